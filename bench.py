@@ -1,10 +1,17 @@
 """
 bench.py - the BASELINE.json metric on MI355X: point-scale feature ops/s of the multiscale
-neighborhood-feature path (10M points x 5 scales), with the achieved-HBM roofline figure of the
-dominant kernel and the reference CPU path timed beside it.
+neighborhood-feature path (10M points x 5 scales); with --full also the achieved-HBM roofline figure
+of the dominant kernel and the reference CPU path timed beside it.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+a plain run sets up, warms up, times the K steps and prints the result line (`roofline`, `cpu_baseline`,
+`voxels_per_scale`, `extra_search_passes_per_scale` and the forest stage's share are null).  --full adds what
+takes runs of its own: the CPU baselines (before the GPU is touched), the per-scale info pass, the copy
+bandwidth and both rooflines, config 5's features-only pass.  --dump-outputs DIR writes what the last timed
+step returned (features, and labels for config 5; offsets and indices with --emit-indices) as DIR/<name>.npy;
+the input is seeded, so two builds run with the same arguments can be compared array for array.
 
 a "step" is one pass of the hot path over one batch of synthetic input: all scales of
 process_single_core's scale loop (spatial order -> occupancy indexes -> fused search/moments/eigen
@@ -140,13 +147,51 @@ def parse_args():
                     help="nm_set_overlap value (0 = sequential stages, 1 = pipelining)")
     ap.add_argument("--fuse-scales", type=int, default=None,
                     help="nm_set_fuse_scales value (1 = one search launch walks all scales, 0 = one per scale)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the CPU baselines, both rooflines of the dominant kernel, "
+                         "the copy bandwidth, voxels and extra search passes per scale, the forest stage's share "
+                         "(runs of their own, outside the timed steps)")
     ap.add_argument("--cpu-sample", type=int, default=150000,
-                    help="points of the CPU-baseline sample (0 = skip)")
+                    help="with --full: points of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned as DIR/<name>.npy "
+                         "(see dump_outputs)")
     ap.add_argument("--emit-indices", action="store_true",
                     help="index-emission (parity) mode: a step writes the neighbor index lists of the workload's "
                          "FINEST scale (multiscale.py:103) as CSR instead of features; value = point-scales/s "
                          "of that, roofline adds 8 * mean list length bytes per point-scale (SURVEY 8d)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+# ---- --dump-outputs ---------------------------------------------------------------------------------------
+
+DUMP_BYTES_PER_ARRAY = 24 << 20     # at most two arrays are sampled per run: under 64 MB in all
+DUMP_SEED = 20240229
+
+
+def dump_outputs(directory, arrays, rank=0, world=1):
+    """writes what the last timed step handed to its caller, one DIR/<name>.npy per array (rank r of N > 1:
+    <name>_rank<r>.npy), float64 where the path computes float64 or integers (exact below 2^53), else float32.
+    an array above DUMP_BYTES_PER_ARRAY is written as a sample of its rows: the sorted draw without
+    replacement of numpy.random.RandomState(DUMP_SEED) for that row count, so the same arguments pick the
+    same rows in every run and every build.  `arrays`: name -> tensor on the GPU, rows along axis 0."""
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        n = int(t.shape[0])
+        row_bytes = 8 * max(int(t[0].numel()) if n else 1, 1)
+        keep = DUMP_BYTES_PER_ARRAY // row_bytes
+        if n > keep:
+            rows = np.sort(np.random.RandomState(DUMP_SEED).choice(n, keep, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        host = t.cpu().numpy()
+        host = host.astype(np.float32 if host.dtype in (np.float16, np.float32) else np.float64)
+        suffix = "" if world == 1 else "_rank%d" % rank
+        np.save(os.path.join(directory, name + suffix + ".npy"), host)
 
 
 # ---- CPU baselines (rank 0, N = 1; they run BEFORE the process touches the GPU) ---------------------------
@@ -250,17 +295,28 @@ def bench_emit_indices(args, cfg, cloud, edges, radii, dev, n_cloud):
     torch.cuda.synchronize(dev)
     total = int(idx.shape[0])
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    off, idx = step()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
-    m = int(multiscale.geometry.VoxelFilter(cloud[:, :3], e, device=dev).unique_addresses(cloud[:, :3]).shape[0])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"offsets": off, "indices": idx})
     k_mean = total / float(nq)
-    # algorithmic bytes of one step (SURVEY 8d plus its index term): read the search cloud for the voxelize
-    # (24 N), write and read the unique addresses (16 M), read the queries (24 N), write offsets (8 N) and the
-    # index lists (8 k N)
-    alg_bytes = 24.0 * nq + 16.0 * m + 24.0 * nq + 8.0 * nq + 8.0 * total
     ms = elapsed / args.steps * 1e3
+    roofline, m = None, None
+    if args.full:
+        m = int(multiscale.geometry.VoxelFilter(cloud[:, :3], e, device=dev).unique_addresses(cloud[:, :3]).shape[0])
+        # algorithmic bytes of one step (SURVEY 8d plus its index term): read the search cloud for the voxelize
+        # (24 N), write and read the unique addresses (16 M), read the queries (24 N), write offsets (8 N) and the
+        # index lists (8 k N)
+        alg_bytes = 24.0 * nq + 16.0 * m + 24.0 * nq + 8.0 * nq + 8.0 * total
+        roofline = {"bound": "hbm", "kernel": "nm_voxelize + k_scale_neighbors (count) + k_scale_neighbors (emit)",
+                    "achieved": alg_bytes / (ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": alg_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, "traffic": None,
+                    "alg_bytes_per_step": alg_bytes, "index_bytes_per_point_scale": 8.0 * k_mean,
+                    "note": "whole step, not one launch: the emission is a chain of dependent binary searches "
+                            "in the address array, latency-bound, nowhere near either roofline"}
     record = {
         "metric": "point-scale neighbor-list ops/sec (index emission, parity mode)",
         "value": nq * args.steps / elapsed, "unit": "point-scales/s", "n_gpus": 1, "steps": args.steps,
@@ -270,13 +326,7 @@ def bench_emit_indices(args, cfg, cloud, edges, radii, dev, n_cloud):
                                "(CSR, int64 ranks in the sorted unique voxel addresses)"
                                % (args.workload, n_cloud, e, r),
                    "points_per_gpu": nq, "scales": 1, "parallelism": "tiles1"},
-        "roofline": {"bound": "hbm", "kernel": "nm_voxelize + k_scale_neighbors (count) + k_scale_neighbors (emit)",
-                     "achieved": alg_bytes / (ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": alg_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, "traffic": None,
-                     "alg_bytes_per_step": alg_bytes, "index_bytes_per_point_scale": 8.0 * k_mean,
-                     "note": "whole step, not one launch: the emission is a chain of dependent binary searches "
-                             "in the address array, latency-bound, nowhere near either roofline"},
-        "voxels": m, "mean_neighbors_per_query": k_mean, "cpu_baseline": None,
+        "roofline": roofline, "voxels": m, "mean_neighbors_per_query": k_mean, "cpu_baseline": None,
     }
     print(json.dumps(record))
 
@@ -321,7 +371,7 @@ def main():
         forest_arrays = {k: fixture[k] for k in ("left", "right", "feature", "threshold", "value",
                                                  "roots", "classes")}
         forest_arrays["n_features"] = int(fixture["n_features"])
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0:
         cpu["cpu_baseline"] = cpu_baseline(points, edges, radii, args.cpu_sample)
         # "all host cores", a 1 M-point slice for configs 2-5.  the box gives one GPU's job a share
         # of 16 cpus (more worker processes than that only fight for them, and the box kills a run above its
@@ -411,14 +461,15 @@ def main():
     if os.environ.get("NIMRUD_BENCH_FOREST_EPILOGUE"):
         rt.check(rt.lib.nm_set_forest_mode(rt.ctx, int(os.environ["NIMRUD_BENCH_FOREST_EPILOGUE"])))
 
-    def step():
+    def step():     # -> (features, labels or None): what the caller of the path receives
         if model is None:
-            return features_step()
+            return features_step(), None
         if world > 1:
             feats = features_step()
-            return model._eval(feats, False, True)[1]
+            return feats, model._eval(feats, False, True)[1]
         # config 5: the forest is evaluated inside the search kernel, behind each row's last scale
-        return classification.classify_cloud(cloud, edges, radii, model, fused=fused, out=out)[0]
+        label, feats = classification.classify_cloud(cloud, edges, radii, model, fused=fused, out=out)
+        return feats, label
 
     def fence():
         torch.cuda.synchronize(dev)
@@ -446,8 +497,9 @@ def main():
     fence()
     rt.lib.nm_profile_begin(rt.ctx)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    last_features, last_labels = step()
     fence()
     elapsed = time.perf_counter() - t0
     import ctypes
@@ -455,10 +507,17 @@ def main():
     launches = ctypes.c_int64(0)
     rt.check(rt.lib.nm_profile_end(rt.ctx, ctypes.byref(ms), ctypes.byref(launches)))
     rt.check_async(wait=True)
+    if args.dump_outputs:
+        arrays = {"features": last_features}
+        if last_labels is not None:
+            arrays["labels"] = last_labels
+        dump_outputs(args.dump_outputs, arrays, rank, world)
+    del last_features, last_labels
+    # everything from here to the record is --full: runs of their own, outside the timed region
     # config 5: the forest stage's share = the step with it minus the same step without (outside the timed
     # region)
     features_only_ms = None
-    if model is not None:
+    if args.full and model is not None:
         for _ in range(2):
             features_step()
         fence()
@@ -469,14 +528,16 @@ def main():
         features_only_ms = (time.perf_counter() - t1) / args.steps * 1e3
 
     # occupied voxels per scale (for the algorithmic byte count), outside the timed region
-    if world == 1:
-        _, info = multiscale.process_gpu(cloud, cloud, edges, radii, return_info=True)
-    else:
-        plan.want_info = True
-        parallel.process_tile(plan)
-        info = plan.last_info()
-    voxels = [i.voxels for i in info]
-    extra_passes = [i.extra_passes for i in info]
+    voxels = extra_passes = None
+    if args.full:
+        if world == 1:
+            _, info = multiscale.process_gpu(cloud, cloud, edges, radii, return_info=True)
+        else:
+            plan.want_info = True
+            parallel.process_tile(plan)
+            info = plan.last_info()
+        voxels = [i.voxels for i in info]
+        extra_passes = [i.extra_passes for i in info]
     n_local_search = cloud.shape[0] if world == 1 else plan.search_points()
 
     if world > 1:
@@ -492,7 +553,7 @@ def main():
     # what a plain device-to-device copy reaches on this box ("report fraction of both nominal
     # and measured-copy bandwidth"); outside the timed region
     copy_gbps = None
-    if rank == 0:
+    if args.full and rank == 0:
         src = torch.empty(1 << 27, dtype=torch.float64, device=dev)      # 1 GiB
         dst = torch.empty_like(src)
         dst.copy_(src)
@@ -507,36 +568,38 @@ def main():
 
     if rank == 0:
         nq = cloud.shape[0]
-        # dominant kernel = k_scale_features<7>: per launch it reads the query coordinates (24 B) and
-        # the occupied-voxel set (8 B per voxel as addresses) and writes 4 fp64 features (32 B).
-        # (with the scales of the ladder in one launch - the default - that launch does this once per scale:
-        # the bytes below are per launch, whatever the launch covers)
-        n_launch = max(launches.value, 1) / max(args.steps, 1)
-        alg_bytes = float(np.sum([56.0 * nq + 8.0 * m for m in voxels])) / n_launch
-        k_ms = ms[2] / max(launches.value, 1)
-        achieved = alg_bytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
-        kernel_name = "k_scale_features<7, 3, true" if (classify and fused) else "k_scale_features<7, 3, false"
-        traffic, traffic_src = measured_traffic(nq, kernel_name) if world == 1 else (None, None)
-        roofline = {
-            "bound": "hbm",
-            "kernel": kernel_name + ", ...> (search + moments + eigen-solve%s)" % (
-                " + forest epilogue" if (classify and fused) else ""),
-            "scales_per_launch": n_scales / n_launch,
-            "achieved": achieved,
-            "peak": HBM_PEAK_GBPS,
-            "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBPS,
-            "measured_copy_GBps": copy_gbps,
-            "frac_of_measured_copy": achieved / copy_gbps if copy_gbps else None,
-            "traffic": traffic,
-            "traffic_source": traffic_src,
-            "alg_bytes_per_launch": alg_bytes,
-            "kernel_ms_avg": k_ms,
-            "valu": valu_ceiling(nq * n_scales / n_launch, k_ms) if (k_ms > 0 and not classify) else None,
-            "note": "nominal bound is HBM (few bytes per unit of work); the binding ceiling is vector-ALU "
-                    "issue, see `valu`: instructions per wave, fp64 flop per query and the fraction of the "
-                    "fp64 vector peak they amount to at the measured query rate",
-        }
+        roofline = None
+        if args.full:
+            # dominant kernel = k_scale_features<7>: per launch it reads the query coordinates (24 B) and
+            # the occupied-voxel set (8 B per voxel as addresses) and writes 4 fp64 features (32 B).
+            # (with the scales of the ladder in one launch - the default - that launch does this once per scale:
+            # the bytes below are per launch, whatever the launch covers)
+            n_launch = max(launches.value, 1) / max(args.steps, 1)
+            alg_bytes = float(np.sum([56.0 * nq + 8.0 * m for m in voxels])) / n_launch
+            k_ms = ms[2] / max(launches.value, 1)
+            achieved = alg_bytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
+            kernel_name = "k_scale_features<7, 3, true" if (classify and fused) else "k_scale_features<7, 3, false"
+            traffic, traffic_src = measured_traffic(nq, kernel_name) if world == 1 else (None, None)
+            roofline = {
+                "bound": "hbm",
+                "kernel": kernel_name + ", ...> (search + moments + eigen-solve%s)" % (
+                    " + forest epilogue" if (classify and fused) else ""),
+                "scales_per_launch": n_scales / n_launch,
+                "achieved": achieved,
+                "peak": HBM_PEAK_GBPS,
+                "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBPS,
+                "measured_copy_GBps": copy_gbps,
+                "frac_of_measured_copy": achieved / copy_gbps if copy_gbps else None,
+                "traffic": traffic,
+                "traffic_source": traffic_src,
+                "alg_bytes_per_launch": alg_bytes,
+                "kernel_ms_avg": k_ms,
+                "valu": valu_ceiling(nq * n_scales / n_launch, k_ms) if (k_ms > 0 and not classify) else None,
+                "note": "nominal bound is HBM (few bytes per unit of work); the binding ceiling is vector-ALU "
+                        "issue, see `valu`: instructions per wave, fp64 flop per query and the fraction of the "
+                        "fp64 vector peak they amount to at the measured query rate",
+            }
         if classify:
             metric, unit = "classified points/sec end-to-end (features + forest)", "points/s"
             value = total_points * args.steps / elapsed

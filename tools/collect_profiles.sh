@@ -6,7 +6,7 @@ set -u
 R=$PWD
 OUT=$R/gpurun_out/${1:-final}
 rm -rf "$OUT"; mkdir -p "$OUT"
-timeout -k 10 300 python3 "$R/bench.py" --steps 10 --warmup 3 > "$OUT/bench_clean.json" 2> "$OUT/bench_clean.err" || echo "bench failed"
+timeout -k 10 300 python3 "$R/bench.py" --full --steps 10 --warmup 3 > "$OUT/bench_clean.json" 2> "$OUT/bench_clean.err" || echo "bench failed"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 "$R/bench.py" --steps 5 --warmup 2 --cpu-sample 0 > "$OUT/trace.json" 2> "$OUT/trace.err" || echo "trace failed"
 for P in "FETCH_SIZE" "WRITE_SIZE" \

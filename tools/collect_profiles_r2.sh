@@ -7,11 +7,11 @@ set -u
 R=$PWD
 OUT=$R/gpurun_out/${1:-r2_final}
 rm -rf "$OUT"; mkdir -p "$OUT"
-timeout -k 10 400 python3 "$R/bench.py" --steps 10 --warmup 3 > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err" || echo "bench c3 failed"
-timeout -k 10 300 python3 "$R/bench.py" --workload c5_scene_10m_rf --steps 10 --warmup 3 --cpu-sample 30000 > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err" || echo "bench c5 failed"
-timeout -k 10 300 python3 "$R/bench.py" --workload c1_uniform_100k --steps 50 --warmup 10 --cpu-sample 0 > "$OUT/bench_c1.json" 2> "$OUT/bench_c1.err" || echo "bench c1 failed"
-timeout -k 10 300 python3 "$R/bench.py" --workload c2_scene_1m --steps 20 --warmup 5 --cpu-sample 0 > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err" || echo "bench c2 failed"
-timeout -k 10 300 python3 "$R/bench.py" --steps 10 --warmup 3 --cpu-sample 0 --fuse-scales 0 > "$OUT/bench_c3_perscale.json" 2> "$OUT/bench_c3_perscale.err" || echo "bench c3 per-scale failed"
+timeout -k 10 400 python3 "$R/bench.py" --full --steps 10 --warmup 3 > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err" || echo "bench c3 failed"
+timeout -k 10 300 python3 "$R/bench.py" --full --workload c5_scene_10m_rf --steps 10 --warmup 3 --cpu-sample 30000 > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err" || echo "bench c5 failed"
+timeout -k 10 300 python3 "$R/bench.py" --full --workload c1_uniform_100k --steps 50 --warmup 10 --cpu-sample 0 > "$OUT/bench_c1.json" 2> "$OUT/bench_c1.err" || echo "bench c1 failed"
+timeout -k 10 300 python3 "$R/bench.py" --full --workload c2_scene_1m --steps 20 --warmup 5 --cpu-sample 0 > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err" || echo "bench c2 failed"
+timeout -k 10 300 python3 "$R/bench.py" --full --steps 10 --warmup 3 --cpu-sample 0 --fuse-scales 0 > "$OUT/bench_c3_perscale.json" 2> "$OUT/bench_c3_perscale.err" || echo "bench c3 per-scale failed"
 echo "benches done"
 cd /tmp && export TMPDIR=/tmp
 trace() {   # name, command...

@@ -10,7 +10,7 @@ OUT=$R/gpurun_out/${1:-r3_final}
 rm -rf "$OUT"; mkdir -p "$OUT"
 b() {  # name args...
   local name=$1; shift
-  timeout -k 10 400 python3 "$R/bench.py" "$@" > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err" || echo "bench $name failed"
+  timeout -k 10 400 python3 "$R/bench.py" --full "$@" > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err" || echo "bench $name failed"
 }
 b c3 --steps 20 --warmup 3
 b c5 --workload c5_scene_10m_rf --steps 10 --warmup 3 --cpu-sample 30000
@@ -51,6 +51,6 @@ done
 cd "$R"
 # the multi-rank step rehearsed on one GPU (HIP kernels, gloo transport staged through the host; not a benchmark)
 for N in 2 3; do
-  NIMRUD_BENCH_BACKEND=gloo timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29517 + N)) bench.py --gpus $N --points 4000000 --steps 3 --warmup 1 > "$OUT/bench_rehearsal_${N}rank.json" 2> "$OUT/bench_rehearsal_${N}rank.err" || echo "rehearsal $N failed"
+  NIMRUD_BENCH_BACKEND=gloo timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29517 + N)) bench.py --full --gpus $N --points 4000000 --steps 3 --warmup 1 > "$OUT/bench_rehearsal_${N}rank.json" 2> "$OUT/bench_rehearsal_${N}rank.err" || echo "rehearsal $N failed"
 done
 ls "$OUT"

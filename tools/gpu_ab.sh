@@ -4,8 +4,8 @@ O=gpurun_out/$1; shift; mkdir -p $O
 for rep in 1 2; do
 for V in "$@"; do
   export NIMRUD_HIP_LIBRARY=$GRAFT_REPO_ROOT/build_abl/lib_$V.so
-  timeout -k 10 200 python bench.py --steps 10 --warmup 3 --cpu-sample 0 > $O/c3_${V}_$rep.json 2> $O/c3_${V}_$rep.err || echo "c3 $V failed"
-  timeout -k 10 200 python bench.py --workload c5_scene_10m_rf --steps 10 --warmup 3 --cpu-sample 0 > $O/c5_${V}_$rep.json 2> $O/c5_${V}_$rep.err || echo "c5 $V failed"
+  timeout -k 10 200 python bench.py --full --steps 10 --warmup 3 --cpu-sample 0 > $O/c3_${V}_$rep.json 2> $O/c3_${V}_$rep.err || echo "c3 $V failed"
+  timeout -k 10 200 python bench.py --full --workload c5_scene_10m_rf --steps 10 --warmup 3 --cpu-sample 0 > $O/c5_${V}_$rep.json 2> $O/c5_${V}_$rep.err || echo "c5 $V failed"
   python - <<PY
 import json
 for w in ("c3","c5"):

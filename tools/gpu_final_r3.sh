@@ -4,7 +4,7 @@ O=gpurun_out/${1:-r3_last}; mkdir -p $O
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke exit $?"; tail -1 $O/smoke.log
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo "pytest exit $?" >> $O/pytest.log; tail -3 $O/pytest.log
 grep -q "Memory access fault" $O/pytest.log && exit 1
-timeout -k 10 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench default exit $?"
+timeout -k 10 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench default exit $?"
 python - <<PY
 import json
 d=json.loads(open("$O/bench_default.json").read().strip().splitlines()[-1])

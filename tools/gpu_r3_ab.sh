@@ -21,14 +21,14 @@ PY
 for rep in 1 2; do
 for V in "$@"; do
   export NIMRUD_HIP_LIBRARY=$GRAFT_REPO_ROOT/build_abl/lib_$V.so
-  timeout -k 10 200 python bench.py --steps 20 --warmup 3 --cpu-sample 0 > $O/c3_${V}_$rep.json 2> $O/c3_${V}_$rep.err || echo "c3 $V failed"
+  timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --cpu-sample 0 > $O/c3_${V}_$rep.json 2> $O/c3_${V}_$rep.err || echo "c3 $V failed"
   line $O/c3_${V}_$rep.json "$V rep$rep c3"
   if [ -n "$SMALL" ] && [ $rep = 1 ]; then
-    timeout -k 10 200 python bench.py --workload c1_uniform_100k --steps 200 --warmup 20 --cpu-sample 0 > $O/c1_${V}.json 2> $O/c1_${V}.err || echo "c1 $V failed"
+    timeout -k 10 200 python bench.py --full --workload c1_uniform_100k --steps 200 --warmup 20 --cpu-sample 0 > $O/c1_${V}.json 2> $O/c1_${V}.err || echo "c1 $V failed"
     line $O/c1_${V}.json "$V c1"
-    timeout -k 10 200 python bench.py --workload c2_scene_1m --steps 100 --warmup 10 --cpu-sample 0 > $O/c2_${V}.json 2> $O/c2_${V}.err || echo "c2 $V failed"
+    timeout -k 10 200 python bench.py --full --workload c2_scene_1m --steps 100 --warmup 10 --cpu-sample 0 > $O/c2_${V}.json 2> $O/c2_${V}.err || echo "c2 $V failed"
     line $O/c2_${V}.json "$V c2"
-    timeout -k 10 200 python bench.py --points 1250000 --steps 100 --warmup 10 --cpu-sample 0 > $O/p1250k_${V}.json 2> $O/p1250k_${V}.err || echo "p1250k $V failed"
+    timeout -k 10 200 python bench.py --full --points 1250000 --steps 100 --warmup 10 --cpu-sample 0 > $O/p1250k_${V}.json 2> $O/p1250k_${V}.err || echo "p1250k $V failed"
     line $O/p1250k_${V}.json "$V c3@1.25M"
   fi
 done
