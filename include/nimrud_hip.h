@@ -101,10 +101,11 @@ int nm_bounds(nm_ctx* ctx, const double* d_xyz, int64_t n, int64_t stride,
 /* ---- spatial order ------------------------------------------------------------------------------
  * the order the ladder entry points work in internally (nm_order.hip), exposed for inspection and
  * tests; no reference counterpart (the reference never reorders a cloud).  rows sorted by the
- * compact Z-order key of their cell of `lat` (30 key bits, a wider key loses its low bits):
- * d_order[i] = row of the point in sorted slot i, d_sorted_xyz (n,3) = the coordinates in that order,
- * d_keys_sorted (nullable) = the key of every sorted slot.  radix sort of our own: three passes,
- * per-tile digit counts + one flat scan + a scatter kernel per pass, no look-back.                 */
+ * compact Z-order key of their cell of `lat`.  the key keeps 20 bits and is sorted in two radix passes for
+ * clouds of up to 2^22 points, 30 bits in three passes beyond (nm_order_plan); a wider key loses its low
+ * bits.  d_order[i] = row of the point in sorted slot i, d_sorted_xyz (n,3) = the coordinates in that
+ * order, d_keys_sorted (nullable) = the key of every sorted slot.  radix sort of our own: per-tile digit
+ * counts + one flat scan + a scatter kernel per pass, no look-back.                                 */
 size_t nm_spatial_order_workspace_bytes(int64_t n);
 int nm_spatial_order(nm_ctx* ctx, const double* d_xyz, int64_t n, int64_t stride, const nm_lattice* lat,
                      uint32_t* d_order, double* d_sorted_xyz, uint32_t* d_keys_sorted, void* d_work,
@@ -245,6 +246,39 @@ int nm_scale_neighbors(nm_ctx* ctx,
                        const int64_t* d_addr, int64_t m, const nm_lattice* lat, double radius,
                        int32_t* d_nbr_count, const int64_t* d_nbr_offsets, int64_t* d_nbr_index,
                        void* stream);
+
+/* ---- neighbor lists from the occupancy index (voxel ranks, no address search) ----------------------------
+ * the same lists - positions in np.unique of the search cloud's addresses (geometry.py:148-150), the
+ * indices multiscale.py:103 hands to features.take - from an index that is built ONCE per (search cloud,
+ * lattice) and queried for any number of query clouds and radii.  the workspace holds a dense occupancy
+ * index of the lattice (a 256-byte leaf of 64 row-words per 32x8x8 superblock) and a rank table: per
+ * row-word, the number of occupied cells with a smaller address.  a row-word is 32 consecutive addresses, so
+ * a voxel's np.unique position is rank[word] + popcount(word below its bit): no sort, no address array, no
+ * search, and every list comes out ascending.
+ *   range: lattices with at most 2^21 superblocks, i.e. max(w0-5,0) + max(w1-3,0) + max(w2-3,0) <= 21 for
+ *     the widths w; nm_neighbor_index_workspace_bytes returns 0 and the other entry points NM_ERR_LATTICE
+ *     beyond it (nm_voxelize + nm_scale_neighbors serve every lattice).  the workspace is a function of the
+ *     lattice alone (up to 1.5 GB at the limit) and belongs to the caller for as long as it is queried.
+ *   a workspace built for one lattice must be queried with THAT lattice (same corner, edge and widths).
+ *   nm_neighbor_index_build: d_count (device int64[2]) receives {M = occupied voxels, search points outside
+ *     the lattice}; those points are counted, not indexed (the contract of nm_voxelize's d_count[1]).
+ *     n_search == 0 is NM_OK: M = 0 and every list is empty.
+ *   nm_neighbor_index_addresses: the sorted distinct addresses (what nm_voxelize writes), every occupied cell
+ *     stored at its rank; d_addr_out needs room for min(n_search, cells of the lattice) entries.
+ *   nm_neighbor_index_lists: the two calls of nm_scale_neighbors (counts, then indices at d_nbr_offsets[q]),
+ *     same home cell, same candidate window, same fp64 test ((dx*dx + dy*dy) + dz*dz) <= r*r, bit for bit.
+ *     n_query == 0 is NM_OK.
+ * nothing here waits for the device; all of it is queued on `stream`.                                  */
+size_t nm_neighbor_index_workspace_bytes(int64_t n_search, const nm_lattice* lat);
+int nm_neighbor_index_build(nm_ctx* ctx, const double* d_search, int64_t n_search, int64_t search_stride,
+                            const nm_lattice* lat, int64_t* d_count, void* d_work, size_t work_bytes,
+                            void* stream);
+int nm_neighbor_index_addresses(nm_ctx* ctx, const nm_lattice* lat, const void* d_work, size_t work_bytes,
+                                int64_t* d_addr_out, void* stream);
+int nm_neighbor_index_lists(nm_ctx* ctx, const double* d_query, int64_t n_query, int64_t query_stride,
+                            const nm_lattice* lat, double radius, const void* d_work, size_t work_bytes,
+                            int32_t* d_nbr_count, const int64_t* d_nbr_offsets, int64_t* d_nbr_index,
+                            void* stream);
 
 /* ---- explicit neighborhoods -----------------------------------------------------------------------
  * features.population / centroid / pca (features.py:21-57) for a batch of explicit neighborhoods

@@ -21,7 +21,7 @@ NM_ERR_RADIUS = -5
 NM_ERR_COMM = -6
 NM_COMM_ID_BYTES = 128
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 c_i64 = ctypes.c_int64
 c_i32 = ctypes.c_int32
@@ -96,6 +96,13 @@ SIGNATURES = {
     "nm_scale_neighbors": (ctypes.c_int,
                            [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_i64, _LATP, c_f64, c_ptr, c_ptr,
                             c_ptr, c_ptr]),
+    "nm_neighbor_index_workspace_bytes": (c_size, [c_i64, _LATP]),
+    "nm_neighbor_index_build": (ctypes.c_int,
+                                [c_ptr, c_ptr, c_i64, c_i64, _LATP, c_ptr, c_ptr, c_size, c_ptr]),
+    "nm_neighbor_index_addresses": (ctypes.c_int, [c_ptr, _LATP, c_ptr, c_size, c_ptr, c_ptr]),
+    "nm_neighbor_index_lists": (ctypes.c_int,
+                                [c_ptr, c_ptr, c_i64, c_i64, _LATP, c_f64, c_ptr, c_size, c_ptr, c_ptr,
+                                 c_ptr, c_ptr]),
     "nm_neighborhood_features": (ctypes.c_int,
                                  [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
     "nm_halo_count": (ctypes.c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_i32, c_i32, c_ptr, c_ptr]),

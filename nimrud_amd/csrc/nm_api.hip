@@ -5,7 +5,7 @@
 
 #include "nm_common.h"
 
-extern "C" int nm_abi_version(void) { return 6; }
+extern "C" int nm_abi_version(void) { return 7; }
 
 // nm_create has no context to leave a message in yet: what failed goes to stderr
 #define NM_CREATE_TRY(call)                                                                       \

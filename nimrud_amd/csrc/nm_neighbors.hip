@@ -1,0 +1,456 @@
+// nm_neighbors.hip - neighbor lists from a dense occupancy index with a voxel-rank table.
+//
+// the reference names a search voxel by its position in np.unique of the addresses (geometry.py:148-150) and
+// gathers by it (multiscale.py:103).  a leaf row-word holds 32 consecutive addresses (x is the low address field),
+// so that position is  rank[row-word] + popc(word & bits below)  once rank[] holds, per row-word, the number of
+// occupied cells with a smaller address.  the index is built ONCE per (search cloud, lattice) and then queried
+// for any number of query clouds and radii: no sort, no address array, no search.
+//
+// workspace (nm_neighbor_index_workspace_bytes), S = superblocks of the lattice (at most 2^NM_DENSE_LOG2):
+//   header  256 B      [0] M, written by the scan
+//   leaves  S * 256 B  the dense index: 64 row-words per superblock, leaf number = nm_sb_key
+//   totals  NT * 4 B   occupied cells per piece of a lattice row, in ADDRESS order; scanned in place
+//   partial 8 KB       the scan's per-block sums
+//   rank    S * 256 B  one word per row-word, same layout as the leaves
+#include "nm_common.h"
+
+namespace {
+
+constexpr int NBR_CHUNK_LOG2 = 4;                 // leaves of one (sbz, sby) strip a wave walks: 16
+constexpr int NBR_CHUNK = 1 << NBR_CHUNK_LOG2;
+constexpr int NBR_SCAN_THREADS = 256;
+constexpr int NBR_SCAN_ITEMS = 16;
+constexpr int NBR_SCAN_TILE = NBR_SCAN_THREADS * NBR_SCAN_ITEMS;      // 4096 totals
+constexpr int NBR_SCAN_MAX_BLOCKS = 2048;
+constexpr size_t NBR_HEADER_BYTES = 256;
+
+// address order is (gz, gy, gx) = (sbz, lz, sby, ly, sbx, lx); leaf order is (sbz, sbx, sby) and a leaf's words
+// run (lz, ly).  a lattice row (gz, gy) crosses 2^bx leaves; it is cut into pieces of NBR_CHUNK leaves so that
+// a long thin lattice still has work for every wave.  totals[] has one entry per piece, in address order:
+// index = (gz * rows_y + gy) * pieces + piece.
+struct NbrPlan {
+    uint64_t superblocks;
+    int32_t chunk_log2;      // leaves per piece: min(bx, NBR_CHUNK_LOG2) bits
+    int32_t piece_bits;      // bx - chunk_log2
+    int64_t units;           // (sbz, sby, piece) triples: one wave each
+    int64_t totals;          // entries of totals[]
+    int64_t totals_padded;   // rounded up to whole scan tiles (the pad stays zero)
+    int32_t scan_blocks;
+    int32_t tiles_per_block;
+    size_t off_leaf, off_totals, off_partial, off_rank, bytes;
+};
+
+inline bool nbr_in_range(const LatticeDev& L) { return L.bx + L.by + L.bz <= NM_DENSE_LOG2; }
+
+NbrPlan nbr_plan(const LatticeDev& L)
+{
+    NbrPlan P;
+    P.superblocks = 1ull << (L.bx + L.by + L.bz);
+    P.chunk_log2 = L.bx < NBR_CHUNK_LOG2 ? L.bx : NBR_CHUNK_LOG2;
+    P.piece_bits = L.bx - P.chunk_log2;
+    P.units = (int64_t)1 << (L.bz + L.by + P.piece_bits);
+    P.totals = P.units * NM_LEAF_WORDS;
+    const int64_t tiles = (P.totals + NBR_SCAN_TILE - 1) / NBR_SCAN_TILE;
+    P.totals_padded = tiles * NBR_SCAN_TILE;
+    P.scan_blocks = (int32_t)(tiles < NBR_SCAN_MAX_BLOCKS ? tiles : NBR_SCAN_MAX_BLOCKS);
+    P.tiles_per_block = (int32_t)((tiles + P.scan_blocks - 1) / P.scan_blocks);
+    const size_t leaf_bytes = (size_t)P.superblocks * NM_LEAF_WORDS * 4;
+    P.off_leaf = NBR_HEADER_BYTES;
+    P.off_totals = P.off_leaf + leaf_bytes;
+    P.off_partial = P.off_totals + (size_t)P.totals_padded * 4;
+    P.off_rank = P.off_partial + (size_t)NBR_SCAN_MAX_BLOCKS * 4;
+    P.bytes = P.off_rank + leaf_bytes;
+    return P;
+}
+
+// candidates per axis for a radius / edge ratio: nm_features.hip's candidate_width, restated here because that
+// translation unit keeps it to itself.  a superset is harmless: every candidate is tested exactly.
+int nbr_candidate_width(double radius, double edge, int32_t* dmin)
+{
+    double rho = radius / edge;
+    double m = floor(rho + 0.5 + 1e-9);
+    if (!(m >= 0.0) || m > 1000.0) return -1;
+    *dmin = -(int32_t)m;
+    return 2 * (int32_t)m + 1;
+}
+
+// ---- build: the cell of every search point, one atomicOr into its row-word --------------------------------------
+__global__ __launch_bounds__(256) void k_nbr_build(const double* __restrict__ xyz, int64_t n, int64_t stride,
+                                                   LatticeDev L, uint32_t* __restrict__ leaf,
+                                                   int64_t* __restrict__ oob_count)
+{
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    bool oob = false;
+    if (i < n) {
+        const double* p = xyz + i * stride;
+        const double fx = nm_cell_f(p[0], L.min_x, L.edge);
+        const double fy = nm_cell_f(p[1], L.min_y, L.edge);
+        const double fz = nm_cell_f(p[2], L.min_z, L.edge);
+        // the contract of nm_voxelize's d_count[1] (k_addresses); NaN coordinates fail every comparison: outside
+        const bool in = fx >= 0.0 && fy >= 0.0 && fz >= 0.0 && fx < (double)(1u << L.wx) &&
+                        fy < (double)(1u << L.wy) && fz < (double)(1u << L.wz);
+        oob = !in;
+        if (in) {
+            const uint32_t cx = (uint32_t)fx, cy = (uint32_t)fy, cz = (uint32_t)fz;
+            const uint64_t sb = nm_sb_key(cx >> NM_SBX_BITS, cy >> NM_SBY_BITS, cz >> NM_SBZ_BITS, L);
+            atomicOr(&leaf[sb * NM_LEAF_WORDS + (((cz & 7u) << 3) | (cy & 7u))], 1u << (cx & 31u));
+        }
+    }
+    const unsigned long long m = __ballot(oob);
+    if (m && (threadIdx.x & 63) == 0)
+        atomicAdd((unsigned long long*)oob_count, (unsigned long long)__popcll(m));
+}
+
+// ---- rank table ---------------------------------------------------------------------------------------------------
+// one wave per (sbz, sby, piece): lane w = lz*8 + ly holds row-word w of every leaf it walks, so each leaf is one
+// 256-byte read of the wave.  the walk's loads are issued together (the leaves are a fixed stride apart).
+// first_leaf: the leaf of the piece's first superblock; total_at: where this lane's piece of a row sits in totals[]
+__device__ __forceinline__ bool nbr_unit(const LatticeDev& L, int32_t chunk_log2, int32_t piece_bits, int64_t units,
+                                         int lane, uint64_t* first_leaf, int64_t* total_at)
+{
+    const int64_t u = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (u >= units) return false;
+    const uint32_t piece = (uint32_t)(u & (((int64_t)1 << piece_bits) - 1));
+    const uint32_t sby = (uint32_t)((u >> piece_bits) & ((1u << L.by) - 1u));
+    const uint32_t sbz = (uint32_t)(u >> (piece_bits + L.by));
+    *first_leaf = nm_sb_key(piece << chunk_log2, sby, sbz, L);
+    const int64_t gz = ((int64_t)sbz << 3) | (lane >> 3), gy = ((int64_t)sby << 3) | (lane & 7);
+    *total_at = (((gz << (L.by + 3)) | gy) << piece_bits) | piece;
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_nbr_row_totals(const uint32_t* __restrict__ leaf, LatticeDev L,
+                                                        int32_t chunk_log2, int32_t piece_bits, int64_t units,
+                                                        uint32_t* __restrict__ totals)
+{
+    const int lane = threadIdx.x & 63;
+    uint64_t first;
+    int64_t at;
+    if (!nbr_unit(L, chunk_log2, piece_bits, units, lane, &first, &at)) return;
+    const int32_t leaves = 1 << chunk_log2;
+    const uint64_t step = (uint64_t)NM_LEAF_WORDS << L.by;        // the next superblock along x
+    const uint32_t* p = leaf + first * NM_LEAF_WORDS + lane;
+    uint32_t v[NBR_CHUNK];
+#pragma unroll
+    for (int i = 0; i < NBR_CHUNK; ++i) v[i] = i < leaves ? p[(uint64_t)i * step] : 0u;
+    uint32_t t = 0;
+#pragma unroll
+    for (int i = 0; i < NBR_CHUNK; ++i) t += (uint32_t)__popc(v[i]);
+    totals[at] = t;
+}
+
+__global__ __launch_bounds__(256) void k_nbr_rank(const uint32_t* __restrict__ leaf, LatticeDev L,
+                                                  int32_t chunk_log2, int32_t piece_bits, int64_t units,
+                                                  const uint32_t* __restrict__ totals, uint32_t* __restrict__ rank)
+{
+    const int lane = threadIdx.x & 63;
+    uint64_t first;
+    int64_t at;
+    if (!nbr_unit(L, chunk_log2, piece_bits, units, lane, &first, &at)) return;
+    const int32_t leaves = 1 << chunk_log2;
+    const uint64_t step = (uint64_t)NM_LEAF_WORDS << L.by;
+    const uint64_t base = first * NM_LEAF_WORDS + lane;
+    uint32_t v[NBR_CHUNK];
+#pragma unroll
+    for (int i = 0; i < NBR_CHUNK; ++i) v[i] = i < leaves ? leaf[base + (uint64_t)i * step] : 0u;
+    uint32_t run = totals[at];       // (scanned: occupied cells before this piece of the row)
+#pragma unroll
+    for (int i = 0; i < NBR_CHUNK; ++i)
+        if (i < leaves) {
+            rank[base + (uint64_t)i * step] = run;
+            run += (uint32_t)__popc(v[i]);
+        }
+}
+
+// ---- flat exclusive scan of totals[], two launches (the shape of nm_order.hip's k_scan_reduce / k_scan_apply) ----
+__device__ __forceinline__ uint32_t nbr_block_sum(uint32_t v, uint32_t* wsum)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    uint32_t t = 0;
+    for (int w = 0; w < NBR_SCAN_THREADS / 64; ++w) t += wsum[w];
+    return t;
+}
+
+__global__ __launch_bounds__(NBR_SCAN_THREADS) void k_nbr_scan_reduce(const uint32_t* __restrict__ totals,
+                                                                      int32_t tiles_per_block,
+                                                                      int64_t len, uint32_t* __restrict__ partial)
+{
+    __shared__ uint32_t wsum[NBR_SCAN_THREADS / 64];
+    uint32_t s = 0;
+    for (int32_t t = 0; t < tiles_per_block; ++t) {
+        const int64_t at = ((int64_t)blockIdx.x * tiles_per_block + t) * NBR_SCAN_TILE +
+                           (int64_t)threadIdx.x * NBR_SCAN_ITEMS;
+        if (at >= len) break;        // len is a multiple of the tile
+        const uint4* p = (const uint4*)(totals + at);
+#pragma unroll
+        for (int q = 0; q < NBR_SCAN_ITEMS / 4; ++q) {
+            const uint4 v = p[q];
+            s += v.x + v.y + v.z + v.w;
+        }
+    }
+    const uint32_t sum = nbr_block_sum(s, wsum);
+    if (threadIdx.x == 0) partial[blockIdx.x] = sum;
+}
+
+__global__ __launch_bounds__(NBR_SCAN_THREADS) void k_nbr_scan_apply(uint32_t* __restrict__ totals,
+                                                                     int32_t tiles_per_block, int64_t len,
+                                                                     const uint32_t* __restrict__ partial,
+                                                                     uint32_t* __restrict__ header,
+                                                                     int64_t* __restrict__ d_count)
+{
+    __shared__ uint32_t wsum[NBR_SCAN_THREADS / 64];
+    __shared__ uint32_t wpre[NBR_SCAN_THREADS / 64];
+    // everything before this block's tiles; block 0 also adds up the rest: M
+    uint32_t before = 0, rest = 0;
+    const int nb = (int)gridDim.x;
+    for (int b = threadIdx.x; b < nb; b += NBR_SCAN_THREADS) {
+        const uint32_t v = (b < (int)blockIdx.x || blockIdx.x == 0) ? partial[b] : 0u;
+        if (b < (int)blockIdx.x) before += v;
+        else rest += v;
+    }
+    before = nbr_block_sum(before, wsum);
+    if (blockIdx.x == 0) {
+        rest = nbr_block_sum(rest, wsum);
+        if (threadIdx.x == 0) {
+            header[0] = rest;
+            d_count[0] = (int64_t)rest;
+        }
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int32_t t = 0; t < tiles_per_block; ++t) {
+        const int64_t at = ((int64_t)blockIdx.x * tiles_per_block + t) * NBR_SCAN_TILE +
+                           (int64_t)threadIdx.x * NBR_SCAN_ITEMS;
+        if (at >= len) break;        // (the same for every thread of the block: len is a multiple of the tile)
+        uint32_t v[NBR_SCAN_ITEMS];
+        uint32_t s = 0;
+        uint4* p = (uint4*)(totals + at);
+#pragma unroll
+        for (int q = 0; q < NBR_SCAN_ITEMS / 4; ++q) {
+            const uint4 x = p[q];
+            v[4 * q] = x.x; v[4 * q + 1] = x.y; v[4 * q + 2] = x.z; v[4 * q + 3] = x.w;
+            s += x.x + x.y + x.z + x.w;
+        }
+        uint32_t incl = s;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t o = __shfl_up(incl, off);
+            if (lane >= off) incl += o;
+        }
+        __syncthreads();       // the readers of wsum / wpre of the round before are done
+        if (lane == 63) wpre[w] = incl;
+        __syncthreads();
+        uint32_t run = before + incl - s;
+        uint32_t tile_sum = 0;
+        for (int ww = 0; ww < NBR_SCAN_THREADS / 64; ++ww) {
+            if (ww < w) run += wpre[ww];
+            tile_sum += wpre[ww];
+        }
+#pragma unroll
+        for (int q = 0; q < NBR_SCAN_ITEMS / 4; ++q) {
+            uint4 x;
+            x.x = run; run += v[4 * q];
+            x.y = run; run += v[4 * q + 1];
+            x.z = run; run += v[4 * q + 2];
+            x.w = run; run += v[4 * q + 3];
+            p[q] = x;
+        }
+        before += tile_sum;
+    }
+}
+
+// ---- addresses: every set bit writes its address at its rank ----------------------------------------------------------
+__global__ __launch_bounds__(256) void k_nbr_addresses(const uint32_t* __restrict__ leaf,
+                                                       const uint32_t* __restrict__ rank,
+                                                       const uint32_t* __restrict__ header, LatticeDev L,
+                                                       uint64_t words, int64_t* __restrict__ out)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= words) return;
+    uint32_t word = leaf[i];
+    if (!word) return;
+    const uint32_t m = header[0];
+    const uint64_t sb = i >> (NM_SBY_BITS + NM_SBZ_BITS);
+    const uint32_t w = (uint32_t)i & (NM_LEAF_WORDS - 1);
+    const int64_t sby = (int64_t)(sb & ((1ull << L.by) - 1ull));
+    const int64_t sbx = (int64_t)((sb >> L.by) & ((1ull << L.bx) - 1ull));
+    const int64_t sbz = (int64_t)(sb >> (L.bx + L.by));
+    const int64_t gy = (sby << 3) | (w & 7u), gz = (sbz << 3) | (w >> 3);
+    const int64_t a0 = (sbx << NM_SBX_BITS) + (gy << L.s0) + (gz << L.s1);
+    uint32_t pos = rank[i];
+    while (word) {
+        const int bit = __ffs((int)word) - 1;
+        word &= word - 1u;
+        if (pos < m) out[pos] = a0 + bit;      // (always, for a workspace built for this lattice)
+        ++pos;
+    }
+}
+
+// ---- lists: one lane per query ------------------------------------------------------------------------------------
+// z outer, y inner, x inside the word: ascending address = ascending rank, the lists come out sorted
+__global__ __launch_bounds__(256) void k_nbr_lists(const double* __restrict__ query, int64_t nq, int64_t qstride,
+                                                   const uint32_t* __restrict__ leaf,
+                                                   const uint32_t* __restrict__ rank, LatticeDev L, double r2,
+                                                   int32_t dmin, int32_t W, int32_t* __restrict__ count,
+                                                   const int64_t* __restrict__ offsets,
+                                                   int64_t* __restrict__ index)
+{
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    const double* p = query + q * qstride;
+    const double qx = p[0], qy = p[1], qz = p[2];
+    const int32_t hx = nm_clamp_cell(nm_cell_f(qx, L.min_x, L.edge));
+    const int32_t hy = nm_clamp_cell(nm_cell_f(qy, L.min_y, L.edge));
+    const int32_t hz = nm_clamp_cell(nm_cell_f(qz, L.min_z, L.edge));
+    int32_t n = 0;
+    int64_t* out = index ? index + offsets[q] : nullptr;
+    // the window clipped to the lattice (home cells are clamped to +-2^30 and |dmin| <= 1000: no overflow)
+    const int32_t x0 = max(hx + dmin, 0), x1 = min(hx + dmin + W - 1, (1 << L.wx) - 1);
+    const int32_t y0 = max(hy + dmin, 0), y1 = min(hy + dmin + W - 1, (1 << L.wy) - 1);
+    const int32_t z0 = max(hz + dmin, 0), z1 = min(hz + dmin + W - 1, (1 << L.wz) - 1);
+    if (x0 <= x1) {
+        for (int32_t gz = z0; gz <= z1; ++gz) {
+            double d = qz - nm_centre(gz, L.min_z, L.edge, L.half_edge);
+            const double dz2 = d * d;
+            for (int32_t gy = y0; gy <= y1; ++gy) {
+                d = qy - nm_centre(gy, L.min_y, L.edge, L.half_edge);
+                const double dy2 = d * d;
+                // dx*dx >= 0 and rounding is monotonic: ((dx*dx + dy2) + dz2) >= fl(dy2 + dz2), so a row this
+                // far away holds no neighbor whatever its words say
+                if (!(dy2 + dz2 <= r2)) continue;
+                const uint32_t wrow = (((uint32_t)gz & 7u) << 3) | ((uint32_t)gy & 7u);
+                for (int32_t sbx = x0 >> NM_SBX_BITS; sbx <= (x1 >> NM_SBX_BITS); ++sbx) {
+                    const uint64_t at = nm_sb_key((uint32_t)sbx, (uint32_t)gy >> NM_SBY_BITS,
+                                                  (uint32_t)gz >> NM_SBZ_BITS, L) * NM_LEAF_WORDS + wrow;
+                    const uint32_t all = leaf[at];
+                    // mask to the x-window
+                    const int32_t base = sbx << NM_SBX_BITS;
+                    const int32_t lo = max(x0 - base, 0), hi = min(x1 - base, 31);
+                    uint32_t word = all & (0xFFFFFFFFu >> (31 - hi)) & (0xFFFFFFFFu << lo);
+                    if (!word) continue;
+                    const uint32_t r0 = rank[at];
+                    while (word) {
+                        const int bit = __ffs((int)word) - 1;
+                        word &= word - 1u;
+                        d = qx - nm_centre(base + bit, L.min_x, L.edge, L.half_edge);
+                        const double s = (d * d + dy2) + dz2;
+                        if (!(s <= r2)) continue;
+                        if (out) out[n] = (int64_t)(r0 + (uint32_t)__popc(all & ((1u << bit) - 1u)));
+                        ++n;
+                    }
+                }
+            }
+        }
+    }
+    if (count) count[q] = n;
+}
+
+// argument checks shared by the three entry points that take a built workspace
+int nbr_check_index(nm_ctx* ctx, const char* who, const nm_lattice* lat, const void* d_work, size_t work_bytes,
+                    LatticeDev* L, NbrPlan* P)
+{
+    int rc = validate_lattice(ctx, lat);
+    if (rc) return rc;
+    *L = make_lattice_dev(lat);
+    if (!nbr_in_range(*L))
+        NM_FAIL(ctx, NM_ERR_LATTICE, "%s: the lattice has 2^%d superblocks, the neighbor index takes at most 2^%d",
+                who, L->bx + L->by + L->bz, NM_DENSE_LOG2);
+    *P = nbr_plan(*L);
+    if (!d_work || work_bytes < P->bytes) NM_FAIL(ctx, NM_ERR_WORKSPACE, "%s: workspace too small", who);
+    return NM_OK;
+}
+
+}  // namespace
+
+extern "C" size_t nm_neighbor_index_workspace_bytes(int64_t n_search, const nm_lattice* lat)
+{
+    if (n_search < 0 || validate_lattice(nullptr, lat) != NM_OK) return 0;
+    const LatticeDev L = make_lattice_dev(lat);
+    if (!nbr_in_range(L)) return 0;
+    return nbr_plan(L).bytes;       // (a function of the lattice alone: every superblock has its leaf)
+}
+
+extern "C" int nm_neighbor_index_build(nm_ctx* ctx, const double* d_search, int64_t n_search,
+                                       int64_t search_stride, const nm_lattice* lat, int64_t* d_count,
+                                       void* d_work, size_t work_bytes, void* stream)
+{
+    NM_ENTER_STREAM(ctx, stream);
+    if (n_search < 0 || n_search >= (int64_t)1 << 31 || search_stride < 3 || (n_search > 0 && !d_search) ||
+        !d_count)
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_build: bad arguments");
+    LatticeDev L;
+    NbrPlan P;
+    int rc = nbr_check_index(ctx, "nm_neighbor_index_build", lat, d_work, work_bytes, &L, &P);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    char* w = (char*)d_work;
+    uint32_t* header = (uint32_t*)w;
+    uint32_t* leaf = (uint32_t*)(w + P.off_leaf);
+    uint32_t* totals = (uint32_t*)(w + P.off_totals);
+    uint32_t* partial = (uint32_t*)(w + P.off_partial);
+    uint32_t* rank = (uint32_t*)(w + P.off_rank);
+    NM_HIP(ctx, hipMemsetAsync(d_count, 0, 2 * sizeof(int64_t), s));
+    // header, leaves, totals (with their pad) and the scan's partial sums lie back to back
+    NM_HIP(ctx, hipMemsetAsync(w, 0, P.off_rank, s));
+    if (n_search == 0) return NM_OK;      // empty leaves: no list ever reads a rank, M = 0
+    k_nbr_build<<<(int)((n_search + 255) / 256), 256, 0, s>>>(d_search, n_search, search_stride, L, leaf,
+                                                              d_count + 1);
+    const int unit_blocks = (int)((P.units + 3) / 4);
+    k_nbr_row_totals<<<unit_blocks, 256, 0, s>>>(leaf, L, P.chunk_log2, P.piece_bits, P.units, totals);
+    k_nbr_scan_reduce<<<P.scan_blocks, NBR_SCAN_THREADS, 0, s>>>(totals, P.tiles_per_block, P.totals_padded,
+                                                                 partial);
+    k_nbr_scan_apply<<<P.scan_blocks, NBR_SCAN_THREADS, 0, s>>>(totals, P.tiles_per_block, P.totals_padded,
+                                                                partial, header, d_count);
+    k_nbr_rank<<<unit_blocks, 256, 0, s>>>(leaf, L, P.chunk_log2, P.piece_bits, P.units, totals, rank);
+    NM_HIP(ctx, hipGetLastError());
+    return NM_OK;
+}
+
+extern "C" int nm_neighbor_index_addresses(nm_ctx* ctx, const nm_lattice* lat, const void* d_work,
+                                           size_t work_bytes, int64_t* d_addr_out, void* stream)
+{
+    NM_ENTER_STREAM(ctx, stream);
+    if (!d_addr_out) NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_addresses: bad arguments");
+    LatticeDev L;
+    NbrPlan P;
+    int rc = nbr_check_index(ctx, "nm_neighbor_index_addresses", lat, d_work, work_bytes, &L, &P);
+    if (rc) return rc;
+    const char* w = (const char*)d_work;
+    const uint64_t words = P.superblocks * NM_LEAF_WORDS;
+    k_nbr_addresses<<<(unsigned)((words + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+        (const uint32_t*)(w + P.off_leaf), (const uint32_t*)(w + P.off_rank), (const uint32_t*)w, L, words,
+        d_addr_out);
+    NM_HIP(ctx, hipGetLastError());
+    return NM_OK;
+}
+
+extern "C" int nm_neighbor_index_lists(nm_ctx* ctx, const double* d_query, int64_t n_query, int64_t query_stride,
+                                       const nm_lattice* lat, double radius, const void* d_work,
+                                       size_t work_bytes, int32_t* d_nbr_count, const int64_t* d_nbr_offsets,
+                                       int64_t* d_nbr_index, void* stream)
+{
+    NM_ENTER_STREAM(ctx, stream);
+    if (n_query < 0 || query_stride < 3 || (n_query > 0 && !d_query))
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_lists: bad arguments");
+    if (!d_nbr_count && !d_nbr_index)
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_lists: nothing to write");
+    if (d_nbr_index && !d_nbr_offsets)
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_lists: index output needs offsets");
+    LatticeDev L;
+    NbrPlan P;
+    int rc = nbr_check_index(ctx, "nm_neighbor_index_lists", lat, d_work, work_bytes, &L, &P);
+    if (rc) return rc;
+    int32_t dmin = 0;
+    const int W = nbr_candidate_width(radius, lat->edge, &dmin);
+    if (W < 0) NM_FAIL(ctx, NM_ERR_RADIUS, "radius/edge ratio outside the supported range");
+    if (n_query == 0) return NM_OK;
+    const char* w = (const char*)d_work;
+    k_nbr_lists<<<(unsigned)((n_query + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+        d_query, n_query, query_stride, (const uint32_t*)(w + P.off_leaf), (const uint32_t*)(w + P.off_rank), L,
+        radius * radius, dmin, W, d_nbr_count, d_nbr_offsets, d_nbr_index);
+    NM_HIP(ctx, hipGetLastError());
+    return NM_OK;
+}

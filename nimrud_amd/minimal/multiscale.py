@@ -269,33 +269,133 @@ def one_scale_single_core(query_cloud, search_cloud, edge_length, radius, verbos
                                strict=strict)
 
 
-def neighbor_lists(query_cloud, search_cloud, edge_length, radius):
+class NeighborIndex(object):
+    """the search side of multiscale.py:103, kept: voxel-filter `search_cloud` at `edge_length` once on the
+    device, then ask for the neighbor lists of any number of query clouds and radii (the reference's ladders
+    are one voxel edge with several radii, nimrud/utils/point_clouds.py:29-35).
+
+    method "index" (what "auto" takes wherever it applies): a dense occupancy index of the lattice plus a
+    rank table (nm_neighbor_index_*): the search that finds a neighbor also names it by its np.unique
+    position, nothing is sorted and no address is searched for.  lattices with more than 2^21 superblocks
+    are outside that path's range; for them "auto" falls back to method "search", today's sorted unique
+    addresses (nm_voxelize) searched per candidate cell (nm_scale_neighbors).  same results by contract.
+
+        .method      "index" or "search"
+        .n_voxels    M, the number of occupied voxels
+        .addresses() their sorted distinct addresses (VoxelFilter.unique_addresses)
+        .voxels()    their centres in that order (VoxelFilter.unique_voxels)
+        .lists(query_cloud, radius) -> (offsets int64[Nq+1], index int64[total])
+    torch in, torch out; numpy in, numpy out (addresses / voxels follow the search cloud, lists the query
+    cloud)."""
+
+    def __init__(self, search_cloud, edge_length, method="auto"):
+        if method not in ("auto", "index", "search"):
+            raise ValueError("method must be 'auto', 'index' or 'search'")
+        self._as_torch = isinstance(search_cloud, torch.Tensor)
+        self._source = search_cloud
+        self._rt, self._search = _device.as_cloud(search_cloud)
+        rt, search = self._rt, self._search
+        if search.shape[1] < 3:
+            raise ValueError("only 3D spaces supported by the multiscale pipeline")
+        self.filter = geometry.VoxelFilter(search[:, :3], edge_length, device=rt.device)
+        lat = self.filter.nm_lattice
+        ns = search.shape[0]
+        nbytes = rt.lib.nm_neighbor_index_workspace_bytes(ns, ctypes.byref(lat))
+        if nbytes == 0 and method == "index":
+            raise ValueError("the lattice has more than 2^21 superblocks: outside the range of the neighbor "
+                             "index (method='auto' falls back to the address search)")
+        self.method = "index" if (nbytes and method != "search") else "search"
+        self._m = None
+        self._addr = None
+        if self.method == "search":
+            self._addr = self.filter.unique_addresses(search[:, :3])
+            self._m = int(self._addr.shape[0])
+            return
+        # the handle owns its workspace: it lives as long as the lists are asked for
+        self._work = torch.empty(int(nbytes), dtype=torch.uint8, device=rt.device)
+        self._count = torch.empty(2, dtype=torch.int64, device=rt.device)
+        rt.check(rt.lib.nm_neighbor_index_build(
+            rt.ctx, _device.ptr(search), ns, _device.row_stride(search), ctypes.byref(lat),
+            _device.ptr(self._count), _device.ptr(self._work), self._work.numel(), rt.stream()))
+
+    @property
+    def n_voxels(self):
+        if self._m is None:
+            m, outside = (int(v) for v in self._count.cpu())
+            if outside:     # (cannot happen for the cloud the lattice was made from)
+                raise ValueError("some points fall outside filter bounding region")
+            self._m = m
+        return self._m
+
+    def _addresses_device(self):
+        if self._addr is None:
+            rt = self._rt
+            addr = torch.empty(max(self.n_voxels, 1), dtype=torch.int64, device=rt.device)
+            rt.check(rt.lib.nm_neighbor_index_addresses(
+                rt.ctx, ctypes.byref(self.filter.nm_lattice), _device.ptr(self._work), self._work.numel(),
+                _device.ptr(addr), rt.stream()))
+            self._addr = addr[:self.n_voxels]
+        return self._addr
+
+    def addresses(self):
+        addr = self._addresses_device()
+        return addr if self._as_torch else addr.cpu().numpy()
+
+    def voxels(self):
+        centres = self.filter.address_to_coordinate(self._addresses_device())
+        return centres if self._as_torch else centres.cpu().numpy()
+
+    def _enqueue(self, query, radius, counts, offsets, index):
+        """one of the two calls (counts, or indices at the offsets) on whichever path this handle uses."""
+        rt = self._rt
+        lat = self.filter.nm_lattice
+        nq = query.shape[0]
+        if self.method == "index":
+            rt.check(rt.lib.nm_neighbor_index_lists(
+                rt.ctx, _device.ptr(query), nq, _device.row_stride(query), ctypes.byref(lat), radius,
+                _device.ptr(self._work), self._work.numel(), _device.ptr(counts), _device.ptr(offsets),
+                _device.ptr(index), rt.stream()))
+        else:
+            rt.check(rt.lib.nm_scale_neighbors(
+                rt.ctx, _device.ptr(query), nq, _device.row_stride(query), _device.ptr(self._addr),
+                self._addr.shape[0], ctypes.byref(lat), radius, _device.ptr(counts),
+                _device.ptr(offsets), _device.ptr(index), rt.stream()))
+
+    def lists(self, query_cloud, radius):
+        """(offsets int64[Nq+1], index int64[total]): for every query point the ascending positions, in
+        addresses() / voxels(), of the voxels within `radius`.  the query cloud may be the search cloud
+        the handle was made from (it is then not uploaded again)."""
+        as_torch = isinstance(query_cloud, torch.Tensor)
+        rt = self._rt
+        query = self._search if query_cloud is self._source else _device.as_cloud(query_cloud, rt.device)[1]
+        if query.shape[1] < 3:
+            raise ValueError("only 3D spaces supported by the multiscale pipeline")
+        radius = float(radius)
+        nq = query.shape[0]
+        offsets = torch.zeros(nq + 1, dtype=torch.int64, device=rt.device)
+        total = 0
+        if nq:
+            counts = torch.empty(nq, dtype=torch.int32, device=rt.device)
+            self._enqueue(query, radius, counts, None, None)
+            torch.cumsum(counts, 0, out=offsets[1:])
+            total = int(offsets[-1])
+        index = torch.empty(max(total, 1), dtype=torch.int64, device=rt.device)
+        if total:
+            self._enqueue(query, radius, None, offsets, index)
+        index = index[:total]
+        if as_torch:
+            return offsets, index
+        return offsets.cpu().numpy(), index.cpu().numpy()
+
+
+def neighbor_lists(query_cloud, search_cloud, edge_length, radius, method="auto"):
     """the neighbor index lists of multiscale.py:103 as CSR (offsets int64[Nq+1], index int64[total]):
     for every query point the ascending positions, in the sorted unique voxel array of
-    VoxelFilter.unique_voxels(search_cloud), of the voxels within `radius`.  inspection / parity mode:
-    it searches by address and is much slower than the fused feature path."""
-    shared = query_cloud is search_cloud
-    as_torch = isinstance(query_cloud, torch.Tensor)
-    rt, search = _device.as_cloud(search_cloud)
-    query = search if shared else _device.as_cloud(query_cloud, rt.device)[1]
-    vf = geometry.VoxelFilter(search[:, :3], edge_length, device=rt.device)
-    addr = vf.unique_addresses(search[:, :3])
-    nq = query.shape[0]
-    counts = torch.empty(nq, dtype=torch.int32, device=rt.device)
-    lat = vf.nm_lattice
-    null = ctypes.c_void_p(0)
-    rt.check(rt.lib.nm_scale_neighbors(rt.ctx, _device.ptr(query), nq, _device.row_stride(query),
-                                       _device.ptr(addr), addr.shape[0], ctypes.byref(lat),
-                                       float(radius), _device.ptr(counts), null, null, rt.stream()))
-    offsets = torch.zeros(nq + 1, dtype=torch.int64, device=rt.device)
-    torch.cumsum(counts, 0, out=offsets[1:])
-    total = int(offsets[-1])
-    index = torch.empty(max(total, 1), dtype=torch.int64, device=rt.device)
-    rt.check(rt.lib.nm_scale_neighbors(rt.ctx, _device.ptr(query), nq, _device.row_stride(query),
-                                       _device.ptr(addr), addr.shape[0], ctypes.byref(lat),
-                                       float(radius), null, _device.ptr(offsets), _device.ptr(index),
-                                       rt.stream()))
-    index = index[:total]
-    if as_torch:
-        return offsets, index
-    return offsets.cpu().numpy(), index.cpu().numpy()
+    VoxelFilter.unique_voxels(search_cloud), of the voxels within `radius`.
+    one NeighborIndex, built and asked once - keep the handle yourself to ask again with another radius or
+    query cloud.  method "auto" reads the lists off the occupancy index and its rank table wherever the
+    lattice is in that path's range (every scale of the benchmark configurations) and searches the sorted
+    addresses otherwise; "search" forces the address search (the parity mode of earlier versions, some
+    hundred times slower per point-scale than the fused feature path); "index" raises ValueError when the
+    lattice is out of range.  the results are identical."""
+    return NeighborIndex(search_cloud, edge_length, method=method).lists(query_cloud, radius)
