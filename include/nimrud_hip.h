@@ -280,6 +280,48 @@ int nm_neighbor_index_lists(nm_ctx* ctx, const double* d_query, int64_t n_query,
                             int32_t* d_nbr_count, const int64_t* d_nbr_offsets, int64_t* d_nbr_index,
                             void* stream);
 
+/* ---- attributes on the neighbor index (new symbols only: additive within ABI 7) -----------------------------
+ * the lists name voxels; these carry per-point attributes onto those voxels and reduce them per neighborhood
+ * without writing a list.  exact arithmetic order throughout, so results are reproducible bit for bit.
+ *   nm_neighbor_index_voxel_of: per point the position of its voxel in nm_neighbor_index_addresses (the cell by
+ *     the same fp64 subtract / divide / floor as the build), or -1 where the point lies outside the lattice on
+ *     any axis or in a cell no search point occupies.  for the search cloud the index was built from this is
+ *     np.unique(addresses, return_inverse=True)[1].
+ *   nm_neighbor_index_group: from such voxel numbers (d_voxel[n], values in [0, m) or -1), d_counts[m] = rows
+ *     per voxel (np.bincount), d_start[m+1] = their exclusive prefix sum, d_rows[n] = the rows voxel by voxel,
+ *     ASCENDING within a voxel: np.argsort(d_voxel, kind="stable") once rows of no voxel (-1, or >= m) are
+ *     left out - they are in no segment, and only the first d_start[m] entries of d_rows are written.  the
+ *     result is the same on every run.  d_tmp: nm_neighbor_index_group_workspace_bytes(n) bytes for m <= n,
+ *     (..)(m) bytes otherwise (16-byte aligned); n, m < 2^31.
+ *   nm_neighbor_index_voxel_reduce: d_out[v * dims + c] = the reduction `op` of d_attr[row * attr_stride + c]
+ *     over the rows of voxel v.  NM_REDUCE_SUM adds them left to right in ascending row order starting from 0
+ *     (np.bincount(inverse, weights=column)), NM_REDUCE_MEAN divides that sum once by the count (an IEEE
+ *     division), NM_REDUCE_MIN / MAX are the plain minimum / maximum.  a voxel without rows gives 0.
+ *   nm_neighbor_index_stats: per query point, over the voxels nm_neighbor_index_lists would list (same walk,
+ *     same test) and the rows d_values[voxel * value_stride + 0..dims) of a voxel table: d_count[q] = how many,
+ *     d_mean[q * out_stride + c] = their sum, added left to right in ascending voxel order, divided once by
+ *     the count, d_min / d_max the minimum / maximum.  a query point with no voxel in reach gets count 0 and
+ *     zeros in all three tables.  any of the four outputs may be NULL, not all of them.
+ *   1 <= dims <= NM_STATS_MAX_DIMS, strides in doubles and at least dims.  NaN attribute values are not
+ *   supported (like NaN coordinates): which of them a minimum or maximum keeps is unspecified.
+ *   errors: NM_ERR_INVALID for bad arguments, NM_ERR_WORKSPACE for too small a workspace, NM_ERR_RADIUS as
+ *   nm_neighbor_index_lists, NM_ERR_LATTICE as every entry point that takes the index.                       */
+#define NM_STATS_MAX_DIMS 16
+enum { NM_REDUCE_MEAN = 0, NM_REDUCE_SUM = 1, NM_REDUCE_MIN = 2, NM_REDUCE_MAX = 3 };
+int nm_neighbor_index_voxel_of(nm_ctx* ctx, const double* d_points, int64_t n, int64_t stride,
+                               const nm_lattice* lat, const void* d_work, size_t work_bytes, int64_t* d_voxel,
+                               void* stream);
+size_t nm_neighbor_index_group_workspace_bytes(int64_t n_points);
+int nm_neighbor_index_group(nm_ctx* ctx, const int64_t* d_voxel, int64_t n, int64_t m, int64_t* d_counts,
+                            int64_t* d_start, int64_t* d_rows, void* d_tmp, size_t tmp_bytes, void* stream);
+int nm_neighbor_index_voxel_reduce(nm_ctx* ctx, const int64_t* d_start, const int64_t* d_rows, int64_t m,
+                                   const double* d_attr, int64_t attr_stride, int32_t dims, int32_t op,
+                                   double* d_out, void* stream);
+int nm_neighbor_index_stats(nm_ctx* ctx, const double* d_query, int64_t n_query, int64_t query_stride,
+                            const nm_lattice* lat, double radius, const void* d_work, size_t work_bytes,
+                            const double* d_values, int64_t value_stride, int32_t dims, int32_t* d_count,
+                            double* d_mean, double* d_min, double* d_max, int64_t out_stride, void* stream);
+
 /* ---- explicit neighborhoods -----------------------------------------------------------------------
  * features.population / centroid / pca (features.py:21-57) for a batch of explicit neighborhoods
  * given as CSR over a point array: neighborhood b is d_points[d_offsets[b] .. d_offsets[b+1]) (rows

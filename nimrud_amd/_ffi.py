@@ -22,6 +22,8 @@ NM_ERR_COMM = -6
 NM_COMM_ID_BYTES = 128
 
 ABI_VERSION = 7
+NM_STATS_MAX_DIMS = 16
+NM_REDUCE = {"mean": 0, "sum": 1, "min": 2, "max": 3}      # NM_REDUCE_MEAN .. NM_REDUCE_MAX
 
 c_i64 = ctypes.c_int64
 c_i32 = ctypes.c_int32
@@ -103,6 +105,16 @@ SIGNATURES = {
     "nm_neighbor_index_lists": (ctypes.c_int,
                                 [c_ptr, c_ptr, c_i64, c_i64, _LATP, c_f64, c_ptr, c_size, c_ptr, c_ptr,
                                  c_ptr, c_ptr]),
+    "nm_neighbor_index_voxel_of": (ctypes.c_int,
+                                   [c_ptr, c_ptr, c_i64, c_i64, _LATP, c_ptr, c_size, c_ptr, c_ptr]),
+    "nm_neighbor_index_group_workspace_bytes": (c_size, [c_i64]),
+    "nm_neighbor_index_group": (ctypes.c_int,
+                                [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "nm_neighbor_index_voxel_reduce": (ctypes.c_int,
+                                       [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_i32, c_i32, c_ptr, c_ptr]),
+    "nm_neighbor_index_stats": (ctypes.c_int,
+                                [c_ptr, c_ptr, c_i64, c_i64, _LATP, c_f64, c_ptr, c_size, c_ptr, c_i64, c_i32,
+                                 c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
     "nm_neighborhood_features": (ctypes.c_int,
                                  [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
     "nm_halo_count": (ctypes.c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_i32, c_i32, c_ptr, c_ptr]),

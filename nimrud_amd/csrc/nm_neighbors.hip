@@ -5,6 +5,8 @@
 // so that position is  rank[row-word] + popc(word & bits below)  once rank[] holds, per row-word, the number of
 // occupied cells with a smaller address.  the index is built ONCE per (search cloud, lattice) and then queried
 // for any number of query clouds and radii: no sort, no address array, no search.
+// on the same index, attributes: the voxel of a point (np.unique's inverse), the rows of every voxel, per-voxel
+// reductions of per-point columns, and per-neighborhood count / mean / min / max of a voxel table without a list.
 //
 // workspace (nm_neighbor_index_workspace_bytes), S = superblocks of the lattice (at most 2^NM_DENSE_LOG2):
 //   header  256 B      [0] M, written by the scan
@@ -289,8 +291,57 @@ __global__ __launch_bounds__(256) void k_nbr_addresses(const uint32_t* __restric
     }
 }
 
-// ---- lists: one lane per query ------------------------------------------------------------------------------------
-// z outer, y inner, x inside the word: ascending address = ascending rank, the lists come out sorted
+// ---- the window walk: one lane per query ---------------------------------------------------------------------------
+// z outer, y inner, x inside the word: ascending address = ascending rank, so hit(voxel) is called in ascending
+// voxel order.  shared by the lists and the neighborhood statistics: same clamped home cell, same clipping, same
+// row skip, same unfused test
+template <typename F>
+__device__ __forceinline__ void nbr_walk(double qx, double qy, double qz, const uint32_t* __restrict__ leaf,
+                                         const uint32_t* __restrict__ rank, const LatticeDev& L, double r2,
+                                         int32_t dmin, int32_t W, F&& hit)
+{
+    const int32_t hx = nm_clamp_cell(nm_cell_f(qx, L.min_x, L.edge));
+    const int32_t hy = nm_clamp_cell(nm_cell_f(qy, L.min_y, L.edge));
+    const int32_t hz = nm_clamp_cell(nm_cell_f(qz, L.min_z, L.edge));
+    // the window clipped to the lattice (home cells are clamped to +-2^30 and |dmin| <= 1000: no overflow)
+    const int32_t x0 = max(hx + dmin, 0), x1 = min(hx + dmin + W - 1, (1 << L.wx) - 1);
+    const int32_t y0 = max(hy + dmin, 0), y1 = min(hy + dmin + W - 1, (1 << L.wy) - 1);
+    const int32_t z0 = max(hz + dmin, 0), z1 = min(hz + dmin + W - 1, (1 << L.wz) - 1);
+    if (x0 > x1) return;
+    for (int32_t gz = z0; gz <= z1; ++gz) {
+        double d = qz - nm_centre(gz, L.min_z, L.edge, L.half_edge);
+        const double dz2 = d * d;
+        for (int32_t gy = y0; gy <= y1; ++gy) {
+            d = qy - nm_centre(gy, L.min_y, L.edge, L.half_edge);
+            const double dy2 = d * d;
+            // dx*dx >= 0 and rounding is monotonic: ((dx*dx + dy2) + dz2) >= fl(dy2 + dz2), so a row this
+            // far away holds no neighbor whatever its words say
+            if (!(dy2 + dz2 <= r2)) continue;
+            const uint32_t wrow = (((uint32_t)gz & 7u) << 3) | ((uint32_t)gy & 7u);
+            for (int32_t sbx = x0 >> NM_SBX_BITS; sbx <= (x1 >> NM_SBX_BITS); ++sbx) {
+                const uint64_t at = nm_sb_key((uint32_t)sbx, (uint32_t)gy >> NM_SBY_BITS,
+                                              (uint32_t)gz >> NM_SBZ_BITS, L) * NM_LEAF_WORDS + wrow;
+                const uint32_t all = leaf[at];
+                // mask to the x-window
+                const int32_t base = sbx << NM_SBX_BITS;
+                const int32_t lo = max(x0 - base, 0), hi = min(x1 - base, 31);
+                uint32_t word = all & (0xFFFFFFFFu >> (31 - hi)) & (0xFFFFFFFFu << lo);
+                if (!word) continue;
+                const uint32_t r0 = rank[at];
+                while (word) {
+                    const int bit = __ffs((int)word) - 1;
+                    word &= word - 1u;
+                    d = qx - nm_centre(base + bit, L.min_x, L.edge, L.half_edge);
+                    const double s = (d * d + dy2) + dz2;
+                    if (!(s <= r2)) continue;
+                    hit(r0 + (uint32_t)__popc(all & ((1u << bit) - 1u)));
+                }
+            }
+        }
+    }
+}
+
+// ---- lists: the voxels the walk finds, counted or written at the query's offset ---------------------------------
 __global__ __launch_bounds__(256) void k_nbr_lists(const double* __restrict__ query, int64_t nq, int64_t qstride,
                                                    const uint32_t* __restrict__ leaf,
                                                    const uint32_t* __restrict__ rank, LatticeDev L, double r2,
@@ -301,54 +352,274 @@ __global__ __launch_bounds__(256) void k_nbr_lists(const double* __restrict__ qu
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= nq) return;
     const double* p = query + q * qstride;
-    const double qx = p[0], qy = p[1], qz = p[2];
-    const int32_t hx = nm_clamp_cell(nm_cell_f(qx, L.min_x, L.edge));
-    const int32_t hy = nm_clamp_cell(nm_cell_f(qy, L.min_y, L.edge));
-    const int32_t hz = nm_clamp_cell(nm_cell_f(qz, L.min_z, L.edge));
     int32_t n = 0;
     int64_t* out = index ? index + offsets[q] : nullptr;
-    // the window clipped to the lattice (home cells are clamped to +-2^30 and |dmin| <= 1000: no overflow)
-    const int32_t x0 = max(hx + dmin, 0), x1 = min(hx + dmin + W - 1, (1 << L.wx) - 1);
-    const int32_t y0 = max(hy + dmin, 0), y1 = min(hy + dmin + W - 1, (1 << L.wy) - 1);
-    const int32_t z0 = max(hz + dmin, 0), z1 = min(hz + dmin + W - 1, (1 << L.wz) - 1);
-    if (x0 <= x1) {
-        for (int32_t gz = z0; gz <= z1; ++gz) {
-            double d = qz - nm_centre(gz, L.min_z, L.edge, L.half_edge);
-            const double dz2 = d * d;
-            for (int32_t gy = y0; gy <= y1; ++gy) {
-                d = qy - nm_centre(gy, L.min_y, L.edge, L.half_edge);
-                const double dy2 = d * d;
-                // dx*dx >= 0 and rounding is monotonic: ((dx*dx + dy2) + dz2) >= fl(dy2 + dz2), so a row this
-                // far away holds no neighbor whatever its words say
-                if (!(dy2 + dz2 <= r2)) continue;
-                const uint32_t wrow = (((uint32_t)gz & 7u) << 3) | ((uint32_t)gy & 7u);
-                for (int32_t sbx = x0 >> NM_SBX_BITS; sbx <= (x1 >> NM_SBX_BITS); ++sbx) {
-                    const uint64_t at = nm_sb_key((uint32_t)sbx, (uint32_t)gy >> NM_SBY_BITS,
-                                                  (uint32_t)gz >> NM_SBZ_BITS, L) * NM_LEAF_WORDS + wrow;
-                    const uint32_t all = leaf[at];
-                    // mask to the x-window
-                    const int32_t base = sbx << NM_SBX_BITS;
-                    const int32_t lo = max(x0 - base, 0), hi = min(x1 - base, 31);
-                    uint32_t word = all & (0xFFFFFFFFu >> (31 - hi)) & (0xFFFFFFFFu << lo);
-                    if (!word) continue;
-                    const uint32_t r0 = rank[at];
-                    while (word) {
-                        const int bit = __ffs((int)word) - 1;
-                        word &= word - 1u;
-                        d = qx - nm_centre(base + bit, L.min_x, L.edge, L.half_edge);
-                        const double s = (d * d + dy2) + dz2;
-                        if (!(s <= r2)) continue;
-                        if (out) out[n] = (int64_t)(r0 + (uint32_t)__popc(all & ((1u << bit) - 1u)));
-                        ++n;
-                    }
-                }
-            }
-        }
-    }
+    nbr_walk(p[0], p[1], p[2], leaf, rank, L, r2, dmin, W, [&](uint32_t voxel) {
+        if (out) out[n] = (int64_t)voxel;
+        ++n;
+    });
     if (count) count[q] = n;
 }
 
-// argument checks shared by the three entry points that take a built workspace
+// ---- point -> voxel: the np.unique inverse -------------------------------------------------------------------------
+// one lane per point: its cell by the reference's own division (as k_nbr_build), the row-word and its rank.
+// -1 outside the lattice on any axis (NaN coordinates fail every comparison) and in a cell nobody occupies
+__global__ __launch_bounds__(256) void k_nbr_voxel_of(const double* __restrict__ xyz, int64_t n, int64_t stride,
+                                                      LatticeDev L, const uint32_t* __restrict__ leaf,
+                                                      const uint32_t* __restrict__ rank,
+                                                      int64_t* __restrict__ voxel)
+{
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double* p = xyz + i * stride;
+    const double fx = nm_cell_f(p[0], L.min_x, L.edge);
+    const double fy = nm_cell_f(p[1], L.min_y, L.edge);
+    const double fz = nm_cell_f(p[2], L.min_z, L.edge);
+    const bool in = fx >= 0.0 && fy >= 0.0 && fz >= 0.0 && fx < (double)(1u << L.wx) &&
+                    fy < (double)(1u << L.wy) && fz < (double)(1u << L.wz);
+    int64_t v = -1;
+    if (in) {
+        const uint32_t cx = (uint32_t)fx, cy = (uint32_t)fy, cz = (uint32_t)fz;
+        const uint64_t at = nm_sb_key(cx >> NM_SBX_BITS, cy >> NM_SBY_BITS, cz >> NM_SBZ_BITS, L) * NM_LEAF_WORDS +
+                            (((cz & 7u) << 3) | (cy & 7u));
+        const uint32_t word = leaf[at], bit = cx & 31u;
+        if ((word >> bit) & 1u) v = (int64_t)(rank[at] + (uint32_t)__popc(word & ((1u << bit) - 1u)));
+    }
+    voxel[i] = v;
+}
+
+// ---- grouping: the rows of every voxel, ascending ----------------------------------------------------------------
+// tmp (nm_neighbor_index_group_workspace_bytes), n rows into m voxels:
+//   header  256 B                  word 0: the scan's total; bytes 16..23: the same as int64 (the scan writes both);
+//                                  word 8: number of long segments
+//   partial 8 KB                   the scan's per-block sums
+//   longs   (n / 64 + 1) * 4 B     the voxels with more than GRP_SHORT rows (there are at most n / 65)
+//   cursor  pad4096(m) * 4 B       per voxel: its count, then (scanned in place) its start, then its fill cursor
+constexpr int GRP_SHORT = 64;           // a segment up to here is ordered by one thread, in place
+constexpr int GRP_LDS_ROWS = 8192;      // a longer one by a block: in LDS up to here (32 KB), else in memory
+constexpr int GRP_LONG_BLOCKS = 1024;
+constexpr int GRP_HEAD_LONGS = 8;
+
+struct GrpPlan {
+    int64_t cursor_len;          // m rounded up to whole scan tiles
+    int32_t scan_blocks, tiles_per_block;
+    size_t off_partial, off_longs, off_cursor, bytes;
+};
+
+GrpPlan grp_plan(int64_t n, int64_t m)
+{
+    GrpPlan G;
+    const int64_t tiles = m > 0 ? (m + NBR_SCAN_TILE - 1) / NBR_SCAN_TILE : 1;
+    G.cursor_len = tiles * NBR_SCAN_TILE;
+    G.scan_blocks = (int32_t)(tiles < NBR_SCAN_MAX_BLOCKS ? tiles : NBR_SCAN_MAX_BLOCKS);
+    G.tiles_per_block = (int32_t)((tiles + G.scan_blocks - 1) / G.scan_blocks);
+    G.off_partial = NBR_HEADER_BYTES;
+    G.off_longs = G.off_partial + (size_t)NBR_SCAN_MAX_BLOCKS * 4;
+    G.off_cursor = G.off_longs + ((size_t)(n / 64 + 1) * 4 + 15) / 16 * 16;     // (16-byte loads of the scan)
+    G.bytes = G.off_cursor + (size_t)G.cursor_len * 4;
+    return G;
+}
+
+__global__ __launch_bounds__(256) void k_grp_zero(uint32_t* __restrict__ header, uint32_t* __restrict__ cursor,
+                                                  int64_t len)
+{
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i < (int64_t)(NBR_HEADER_BYTES / 4)) header[i] = 0u;
+    if (i < len) cursor[i] = 0u;
+}
+
+// integer atomics on the voxel number: exact, whatever the order.  rows of no voxel (-1, or a number past m)
+// are in no segment
+__global__ __launch_bounds__(256) void k_grp_count(const int64_t* __restrict__ voxel, int64_t n, int64_t m,
+                                                   uint32_t* __restrict__ cursor)
+{
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t v = voxel[i];
+    if (v >= 0 && v < m) atomicAdd(&cursor[v], 1u);
+}
+
+__global__ __launch_bounds__(256) void k_grp_put_counts(const uint32_t* __restrict__ cursor, int64_t m,
+                                                        int64_t* __restrict__ counts)
+{
+    const int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (v < m) counts[v] = (int64_t)cursor[v];
+}
+
+__global__ __launch_bounds__(256) void k_grp_put_start(const uint32_t* __restrict__ cursor,
+                                                       const uint32_t* __restrict__ header, int64_t m,
+                                                       int64_t* __restrict__ start)
+{
+    const int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (v < m) start[v] = (int64_t)cursor[v];
+    if (v == m) start[m] = (int64_t)header[0];
+}
+
+// every row takes the next place of its voxel's segment: whichever comes first.  the order is put right below
+__global__ __launch_bounds__(256) void k_grp_fill(const int64_t* __restrict__ voxel, int64_t n, int64_t m,
+                                                  uint32_t* __restrict__ cursor, int64_t* __restrict__ rows)
+{
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t v = voxel[i];
+    if (v >= 0 && v < m) rows[atomicAdd(&cursor[v], 1u)] = i;
+}
+
+// one thread per voxel: a short segment by insertion, in place; a long one is put on the list
+__global__ __launch_bounds__(256) void k_grp_order_short(const int64_t* __restrict__ start, int64_t m,
+                                                         int64_t* __restrict__ rows,
+                                                         uint32_t* __restrict__ header,
+                                                         uint32_t* __restrict__ longs)
+{
+    const int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (v >= m) return;
+    const int64_t s = start[v];
+    const int32_t len = (int32_t)(start[v + 1] - s);
+    if (len > GRP_SHORT) {
+        longs[atomicAdd(&header[GRP_HEAD_LONGS], 1u)] = (uint32_t)v;
+        return;
+    }
+    int64_t* a = rows + s;
+    for (int32_t i = 1; i < len; ++i) {
+        const int64_t x = a[i];
+        int32_t j = i;
+        while (j > 0 && a[j - 1] > x) {
+            a[j] = a[j - 1];
+            --j;
+        }
+        a[j] = x;
+    }
+}
+
+// bitonic network of a block over a[0 .. len), every comparator leaves the smaller value at the smaller place
+// (the merges start with a flip), so the places from len up to the next power of two act as +infinity without
+// existing: a comparator that reaches one does nothing.  len * log2(len)^2 / 4 comparators in all, a 256th of
+// them per thread - whatever the values are
+template <typename T>
+__device__ __forceinline__ void grp_bitonic(T* a, uint32_t len)
+{
+    uint32_t p = 1;
+    while (p < len) p <<= 1;
+    const uint32_t half = p >> 1;
+    for (uint32_t k = 2; k <= p; k <<= 1) {
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            const bool flip = j == (k >> 1);
+            for (uint32_t i = threadIdx.x; i < half; i += blockDim.x) {
+                const uint32_t lo = ((i / j) * (j << 1)) + (i % j);
+                const uint32_t hi = flip ? (lo - (i % j)) + (k - 1u) - (i % j) : lo + j;
+                if (hi < len) {
+                    const T x = a[lo], y = a[hi];
+                    if (x > y) {
+                        a[lo] = y;
+                        a[hi] = x;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// one block per long segment (the blocks share the list out)
+__global__ __launch_bounds__(256) void k_grp_order_long(const int64_t* __restrict__ start, int64_t* __restrict__ rows,
+                                                        const uint32_t* __restrict__ header,
+                                                        const uint32_t* __restrict__ longs)
+{
+    __shared__ uint32_t tile[GRP_LDS_ROWS];
+    const uint32_t n_long = header[GRP_HEAD_LONGS];
+    for (uint32_t at = blockIdx.x; at < n_long; at += gridDim.x) {
+        const uint32_t v = longs[at];
+        const int64_t s = start[v];
+        const uint32_t len = (uint32_t)(start[v + 1] - s);
+        int64_t* a = rows + s;
+        if (len <= GRP_LDS_ROWS) {
+            for (uint32_t i = threadIdx.x; i < len; i += blockDim.x) tile[i] = (uint32_t)a[i];     // rows < 2^31
+            __syncthreads();
+            grp_bitonic(tile, len);
+            for (uint32_t i = threadIdx.x; i < len; i += blockDim.x) a[i] = (int64_t)tile[i];
+        } else {
+            __syncthreads();       // (the fill's stores are another kernel's; this orders the rounds of the loop)
+            grp_bitonic(a, len);
+        }
+        __syncthreads();
+    }
+}
+
+// ---- voxel table: one thread per (voxel, column), the segment left to right ----------------------------------------
+enum { GRP_MEAN = NM_REDUCE_MEAN, GRP_SUM = NM_REDUCE_SUM, GRP_MIN = NM_REDUCE_MIN, GRP_MAX = NM_REDUCE_MAX };
+
+// sum: ((0 + a[r0]) + a[r1]) + ... in ascending row order - np.bincount(inverse, weights=column); mean: that sum,
+// divided once by the count.  a voxel without rows gives 0
+template <int OP>
+__global__ __launch_bounds__(256) void k_nbr_voxel_reduce(const int64_t* __restrict__ start,
+                                                          const int64_t* __restrict__ rows, int64_t m,
+                                                          const double* __restrict__ attr, int64_t astride,
+                                                          int32_t dims, double* __restrict__ out)
+{
+    const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (t >= m * dims) return;
+    const int64_t v = t / dims;
+    const int32_t c = (int32_t)(t - v * dims);
+    const int64_t s = start[v], e = start[v + 1];
+    double acc = 0.0;
+    if (OP == GRP_MEAN || OP == GRP_SUM) {
+        for (int64_t i = s; i < e; ++i) acc += attr[rows[i] * astride + c];
+        if (OP == GRP_MEAN && e > s) acc = acc / (double)(e - s);
+    } else if (e > s) {
+        acc = attr[rows[s] * astride + c];
+        for (int64_t i = s + 1; i < e; ++i) {
+            const double x = attr[rows[i] * astride + c];
+            if (OP == GRP_MIN ? x < acc : x > acc) acc = x;
+        }
+    }
+    out[t] = acc;
+}
+
+// ---- neighborhood statistics: the lists' walk, nothing list-shaped written ---------------------------------------------
+// per included voxel the D values of its table row: count, sum left to right in ascending voxel order, running
+// minimum and maximum, all in registers (DB = the compile-time bucket dims falls in)
+template <int DB>
+__global__ __launch_bounds__(256) void k_nbr_stats(const double* __restrict__ query, int64_t nq, int64_t qstride,
+                                                   const uint32_t* __restrict__ leaf,
+                                                   const uint32_t* __restrict__ rank, LatticeDev L, double r2,
+                                                   int32_t dmin, int32_t W, const double* __restrict__ values,
+                                                   int64_t vstride, int32_t dims, int32_t* __restrict__ count,
+                                                   double* __restrict__ mean, double* __restrict__ vmin,
+                                                   double* __restrict__ vmax, int64_t ostride)
+{
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    const double* p = query + q * qstride;
+    double sum[DB], lo[DB], hi[DB];
+#pragma unroll
+    for (int c = 0; c < DB; ++c) sum[c] = lo[c] = hi[c] = 0.0;
+    int32_t n = 0;
+    nbr_walk(p[0], p[1], p[2], leaf, rank, L, r2, dmin, W, [&](uint32_t voxel) {
+        const double* val = values + (int64_t)voxel * vstride;
+        const bool first = n == 0;
+#pragma unroll
+        for (int c = 0; c < DB; ++c)
+            if (c < dims) {
+                const double x = val[c];
+                sum[c] += x;
+                lo[c] = (first || x < lo[c]) ? x : lo[c];
+                hi[c] = (first || x > hi[c]) ? x : hi[c];
+            }
+        ++n;
+    });
+    if (count) count[q] = n;
+    const double k = (double)n;
+#pragma unroll
+    for (int c = 0; c < DB; ++c)
+        if (c < dims) {
+            // no voxel in reach: zeros in all three tables
+            if (mean) mean[q * ostride + c] = n ? sum[c] / k : 0.0;
+            if (vmin) vmin[q * ostride + c] = lo[c];
+            if (vmax) vmax[q * ostride + c] = hi[c];
+        }
+}
+
+// argument checks shared by the entry points that take a built workspace
 int nbr_check_index(nm_ctx* ctx, const char* who, const nm_lattice* lat, const void* d_work, size_t work_bytes,
                     LatticeDev* L, NbrPlan* P)
 {
@@ -451,6 +722,132 @@ extern "C" int nm_neighbor_index_lists(nm_ctx* ctx, const double* d_query, int64
     k_nbr_lists<<<(unsigned)((n_query + 255) / 256), 256, 0, (hipStream_t)stream>>>(
         d_query, n_query, query_stride, (const uint32_t*)(w + P.off_leaf), (const uint32_t*)(w + P.off_rank), L,
         radius * radius, dmin, W, d_nbr_count, d_nbr_offsets, d_nbr_index);
+    NM_HIP(ctx, hipGetLastError());
+    return NM_OK;
+}
+
+// ---- attributes on the index (additive within ABI 7) -------------------------------------------------------------------
+
+extern "C" int nm_neighbor_index_voxel_of(nm_ctx* ctx, const double* d_points, int64_t n, int64_t stride,
+                                          const nm_lattice* lat, const void* d_work, size_t work_bytes,
+                                          int64_t* d_voxel, void* stream)
+{
+    NM_ENTER_STREAM(ctx, stream);
+    if (n < 0 || stride < 3 || (n > 0 && (!d_points || !d_voxel)))
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_voxel_of: bad arguments");
+    LatticeDev L;
+    NbrPlan P;
+    int rc = nbr_check_index(ctx, "nm_neighbor_index_voxel_of", lat, d_work, work_bytes, &L, &P);
+    if (rc) return rc;
+    if (n == 0) return NM_OK;
+    const char* w = (const char*)d_work;
+    k_nbr_voxel_of<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+        d_points, n, stride, L, (const uint32_t*)(w + P.off_leaf), (const uint32_t*)(w + P.off_rank), d_voxel);
+    NM_HIP(ctx, hipGetLastError());
+    return NM_OK;
+}
+
+extern "C" size_t nm_neighbor_index_group_workspace_bytes(int64_t n_points)
+{
+    if (n_points < 0 || n_points >= (int64_t)1 << 31) return 0;
+    return grp_plan(n_points, n_points).bytes;
+}
+
+extern "C" int nm_neighbor_index_group(nm_ctx* ctx, const int64_t* d_voxel, int64_t n, int64_t m,
+                                       int64_t* d_counts, int64_t* d_start, int64_t* d_rows, void* d_tmp,
+                                       size_t tmp_bytes, void* stream)
+{
+    NM_ENTER_STREAM(ctx, stream);
+    if (n < 0 || n >= (int64_t)1 << 31 || m < 0 || m >= (int64_t)1 << 31 || (n > 0 && (!d_voxel || !d_rows)) ||
+        (m > 0 && !d_counts) || !d_start)
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_group: bad arguments");
+    const GrpPlan G = grp_plan(n, m);
+    if (!d_tmp || tmp_bytes < G.bytes) NM_FAIL(ctx, NM_ERR_WORKSPACE, "nm_neighbor_index_group: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    char* w = (char*)d_tmp;
+    uint32_t* header = (uint32_t*)w;
+    uint32_t* partial = (uint32_t*)(w + G.off_partial);
+    uint32_t* longs = (uint32_t*)(w + G.off_longs);
+    uint32_t* cursor = (uint32_t*)(w + G.off_cursor);
+    const unsigned row_blocks = (unsigned)((n + 255) / 256), voxel_blocks = (unsigned)((m + 1 + 255) / 256);
+    k_grp_zero<<<(unsigned)((G.cursor_len + 255) / 256), 256, 0, s>>>(header, cursor, G.cursor_len);
+    if (n > 0) k_grp_count<<<row_blocks, 256, 0, s>>>(d_voxel, n, m, cursor);
+    if (m > 0) k_grp_put_counts<<<voxel_blocks, 256, 0, s>>>(cursor, m, d_counts);
+    k_nbr_scan_reduce<<<G.scan_blocks, NBR_SCAN_THREADS, 0, s>>>(cursor, G.tiles_per_block, G.cursor_len, partial);
+    k_nbr_scan_apply<<<G.scan_blocks, NBR_SCAN_THREADS, 0, s>>>(cursor, G.tiles_per_block, G.cursor_len, partial,
+                                                                header, (int64_t*)(w + 16));
+    k_grp_put_start<<<voxel_blocks, 256, 0, s>>>(cursor, header, m, d_start);
+    if (n > 0 && m > 0) {
+        k_grp_fill<<<row_blocks, 256, 0, s>>>(d_voxel, n, m, cursor, d_rows);
+        k_grp_order_short<<<voxel_blocks, 256, 0, s>>>(d_start, m, d_rows, header, longs);
+        if (n > GRP_SHORT) {
+            const int64_t most = n / (GRP_SHORT + 1);
+            k_grp_order_long<<<(unsigned)(most < GRP_LONG_BLOCKS ? most : GRP_LONG_BLOCKS), 256, 0, s>>>(
+                d_start, d_rows, header, longs);
+        }
+    }
+    NM_HIP(ctx, hipGetLastError());
+    return NM_OK;
+}
+
+extern "C" int nm_neighbor_index_voxel_reduce(nm_ctx* ctx, const int64_t* d_start, const int64_t* d_rows, int64_t m,
+                                              const double* d_attr, int64_t attr_stride, int32_t dims, int32_t op,
+                                              double* d_out, void* stream)
+{
+    NM_ENTER_STREAM(ctx, stream);
+    if (m < 0 || m >= (int64_t)1 << 31 || dims < 1 || dims > NM_STATS_MAX_DIMS || attr_stride < dims || !d_start ||
+        (m > 0 && (!d_rows || !d_attr || !d_out)) || op < NM_REDUCE_MEAN || op > NM_REDUCE_MAX)
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_voxel_reduce: bad arguments");
+    if (m == 0) return NM_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned blocks = (unsigned)((m * dims + 255) / 256);
+#define NM_REDUCE_LAUNCH(OP) \
+    k_nbr_voxel_reduce<OP><<<blocks, 256, 0, s>>>(d_start, d_rows, m, d_attr, attr_stride, dims, d_out)
+    switch (op) {
+    case NM_REDUCE_MEAN: NM_REDUCE_LAUNCH(GRP_MEAN); break;
+    case NM_REDUCE_SUM: NM_REDUCE_LAUNCH(GRP_SUM); break;
+    case NM_REDUCE_MIN: NM_REDUCE_LAUNCH(GRP_MIN); break;
+    default: NM_REDUCE_LAUNCH(GRP_MAX); break;
+    }
+#undef NM_REDUCE_LAUNCH
+    NM_HIP(ctx, hipGetLastError());
+    return NM_OK;
+}
+
+extern "C" int nm_neighbor_index_stats(nm_ctx* ctx, const double* d_query, int64_t n_query, int64_t query_stride,
+                                       const nm_lattice* lat, double radius, const void* d_work, size_t work_bytes,
+                                       const double* d_values, int64_t value_stride, int32_t dims, int32_t* d_count,
+                                       double* d_mean, double* d_min, double* d_max, int64_t out_stride,
+                                       void* stream)
+{
+    NM_ENTER_STREAM(ctx, stream);
+    if (n_query < 0 || query_stride < 3 || (n_query > 0 && !d_query) || dims < 1 || dims > NM_STATS_MAX_DIMS ||
+        value_stride < dims || !d_values)
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_stats: bad arguments");
+    if (!d_count && !d_mean && !d_min && !d_max)
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_stats: nothing to write");
+    if ((d_mean || d_min || d_max) && out_stride < dims)
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_stats: output stride below the column count");
+    LatticeDev L;
+    NbrPlan P;
+    int rc = nbr_check_index(ctx, "nm_neighbor_index_stats", lat, d_work, work_bytes, &L, &P);
+    if (rc) return rc;
+    int32_t dmin = 0;
+    const int W = nbr_candidate_width(radius, lat->edge, &dmin);
+    if (W < 0) NM_FAIL(ctx, NM_ERR_RADIUS, "radius/edge ratio outside the supported range");
+    if (n_query == 0) return NM_OK;
+    const char* w = (const char*)d_work;
+    const uint32_t* leaf = (const uint32_t*)(w + P.off_leaf);
+    const uint32_t* rank = (const uint32_t*)(w + P.off_rank);
+    const unsigned blocks = (unsigned)((n_query + 255) / 256);
+#define NM_STATS_LAUNCH(DB)                                                                                       \
+    k_nbr_stats<DB><<<blocks, 256, 0, (hipStream_t)stream>>>(d_query, n_query, query_stride, leaf, rank, L,       \
+                                                             radius * radius, dmin, W, d_values, value_stride,    \
+                                                             dims, d_count, d_mean, d_min, d_max, out_stride)
+    if (dims == 1) NM_STATS_LAUNCH(1);
+    else if (dims <= 4) NM_STATS_LAUNCH(4);
+    else NM_STATS_LAUNCH(16);
+#undef NM_STATS_LAUNCH
     NM_HIP(ctx, hipGetLastError());
     return NM_OK;
 }

@@ -63,3 +63,55 @@ def vector_field_mean(query_cloud, search_cloud, attributes, edge_lengths, radii
     """numpy in, numpy out (the clouds and the attribute table cross PCIe)."""
     return vector_field_mean_gpu(np.asarray(query_cloud), np.asarray(search_cloud),
                                  np.asarray(attributes), edge_lengths, radii).cpu().numpy()
+
+
+def vector_field_stats_gpu(query_cloud, search_cloud, attributes, edge_lengths, radii):
+    """(count int32 (Nq, S), mean, vmin, vmax fp64 (Nq, D*S)) GPU tensors: for every scale s, over the voxels
+    within radii[s] of each query point, how many there are and the mean, minimum and maximum of the voxel
+    attributes (a voxel's attribute being the mean of the attributes of the search points in it), scales side
+    by side in caller order.  zeros where no voxel is in reach.
+    the operator of vector_field_mean_gpu on multiscale.NeighborIndex: one handle per DISTINCT edge length
+    serves all of its radii (the reference's ladders are one edge with several radii), sums run in a fixed
+    order (voxel rows ascending, voxels ascending) and every mean is one IEEE division, so results are the
+    same bit for bit on every run.  NaN attribute values are not supported (like NaN coordinates)."""
+    from nimrud_amd.minimal import multiscale
+    assert len(edge_lengths) == len(radii), \
+        "edge_lengths and radii should be equal-length sequences."
+    shared = query_cloud is search_cloud
+    rt, search = _device.as_cloud(search_cloud)
+    query = search if shared else _device.as_cloud(query_cloud, rt.device)[1]
+    if search.shape[1] < 3 or query.shape[1] < 3:
+        raise ValueError("only 3D spaces supported by the multiscale pipeline")
+    if search.shape[0] < 2:
+        raise ValueError("need at least 2 points to define a voxel grid")
+    attr = torch.as_tensor(attributes).to(device=rt.device, dtype=torch.float64)
+    if attr.ndim == 1:
+        attr = attr.reshape(-1, 1)
+    if attr.ndim != 2 or attr.shape[0] != search.shape[0]:
+        raise ValueError("attributes must have one row per search point")
+    dims = int(attr.shape[1])
+    if not 1 <= dims <= MAX_DIMS:
+        raise ValueError("between 1 and %d attribute columns per call" % MAX_DIMS)
+    nq, n_scales = query.shape[0], len(edge_lengths)
+    count = torch.zeros((nq, n_scales), dtype=torch.int32, device=rt.device)
+    mean, vmin, vmax = (torch.zeros((nq, dims * n_scales), dtype=torch.float64, device=rt.device)
+                        for _ in range(3))
+    if n_scales == 0 or nq == 0:
+        return count, mean, vmin, vmax
+    handles = {}
+    for s, (e, r) in enumerate(zip(edge_lengths, radii)):
+        if float(e) not in handles:
+            index = multiscale.NeighborIndex(search, e, method="index")
+            handles[float(e)] = (index, index.voxel_table(attr, reduce="mean"))
+        index, table = handles[float(e)]
+        one = torch.empty(nq, dtype=torch.int32, device=rt.device)
+        block = [ctypes.c_void_p(t.data_ptr() + 8 * dims * s) for t in (mean, vmin, vmax)]
+        index._stats_into(query, r, table, one, block[0], block[1], block[2], dims * n_scales)
+        count[:, s] = one
+    return count, mean, vmin, vmax
+
+
+def vector_field_stats(query_cloud, search_cloud, attributes, edge_lengths, radii):
+    """numpy in, numpy out (the clouds and the attribute table cross PCIe)."""
+    return tuple(t.cpu().numpy() for t in vector_field_stats_gpu(
+        np.asarray(query_cloud), np.asarray(search_cloud), np.asarray(attributes), edge_lengths, radii))

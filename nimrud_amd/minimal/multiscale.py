@@ -25,6 +25,7 @@ import time
 import numpy as np
 import torch
 
+from nimrud_amd import _ffi
 from nimrud_amd import device as _device
 from nimrud_amd.utils import geometry
 
@@ -285,8 +286,15 @@ class NeighborIndex(object):
         .addresses() their sorted distinct addresses (VoxelFilter.unique_addresses)
         .voxels()    their centres in that order (VoxelFilter.unique_voxels)
         .lists(query_cloud, radius) -> (offsets int64[Nq+1], index int64[total])
-    torch in, torch out; numpy in, numpy out (addresses / voxels follow the search cloud, lists the query
-    cloud)."""
+    and, on the index form only (a "search" handle raises ValueError), attributes carried onto those voxels:
+        .voxel_of(points)       which voxel each point falls in (np.unique's inverse; -1 for none)
+        .point_counts()         search points per voxel
+        .members()              (start, rows): the search cloud's rows voxel by voxel, ascending
+        .voxel_table(attributes, reduce="mean")   per-voxel mean / sum / min / max of per-point columns
+        .neighborhood_stats(query_cloud, radius, voxel_values) -> (count, mean, vmin, vmax) per query point
+                                over the voxels lists() would name, without writing the lists
+    torch in, torch out; numpy in, numpy out (addresses / voxels / point_counts / members follow the search
+    cloud, lists / neighborhood_stats the query cloud, voxel_of and voxel_table their argument)."""
 
     def __init__(self, search_cloud, edge_length, method="auto"):
         if method not in ("auto", "index", "search"):
@@ -307,6 +315,7 @@ class NeighborIndex(object):
         self.method = "index" if (nbytes and method != "search") else "search"
         self._m = None
         self._addr = None
+        self._group = None
         if self.method == "search":
             self._addr = self.filter.unique_addresses(search[:, :3])
             self._m = int(self._addr.shape[0])
@@ -386,6 +395,137 @@ class NeighborIndex(object):
         if as_torch:
             return offsets, index
         return offsets.cpu().numpy(), index.cpu().numpy()
+
+    # ---- attributes: from per-point columns to per-neighborhood numbers (method "index" only) ----------------
+
+    def _need_index(self, what):
+        if self.method != "index":
+            raise ValueError("%s needs the index form of the handle (method='index'); this one searches "
+                             "sorted addresses (method='search')" % what)
+
+    def _query_cloud(self, cloud):
+        query = self._search if cloud is self._source else _device.as_cloud(cloud, self._rt.device)[1]
+        if query.shape[1] < 3:
+            raise ValueError("only 3D spaces supported by the multiscale pipeline")
+        return query
+
+    def _voxel_of_device(self, points):
+        rt = self._rt
+        n = points.shape[0]
+        voxel = torch.empty(n, dtype=torch.int64, device=rt.device)
+        rt.check(rt.lib.nm_neighbor_index_voxel_of(
+            rt.ctx, _device.ptr(points), n, _device.row_stride(points), ctypes.byref(self.filter.nm_lattice),
+            _device.ptr(self._work), self._work.numel(), _device.ptr(voxel), rt.stream()))
+        return voxel
+
+    def voxel_of(self, points):
+        """int64 (N,): for every point the position, in addresses() / voxels(), of the voxel it falls in; -1
+        where it lies outside the lattice or in a cell no search point occupies.  for the search cloud itself:
+        np.unique(addresses, return_inverse=True)[1]."""
+        self._need_index("voxel_of")
+        voxel = self._voxel_of_device(self._query_cloud(points))
+        return voxel if isinstance(points, torch.Tensor) else voxel.cpu().numpy()
+
+    def _grouping(self):
+        """(counts (M,), start (M+1,), rows (Ns,)) of the search cloud on the device, made once."""
+        if self._group is None:
+            rt = self._rt
+            m, ns = self.n_voxels, self._search.shape[0]
+            voxel = self._voxel_of_device(self._search)
+            counts = torch.empty(max(m, 1), dtype=torch.int64, device=rt.device)
+            start = torch.empty(m + 1, dtype=torch.int64, device=rt.device)
+            rows = torch.empty(max(ns, 1), dtype=torch.int64, device=rt.device)
+            nbytes = rt.lib.nm_neighbor_index_group_workspace_bytes(max(ns, m))
+            tmp = rt.workspace(nbytes)
+            rt.check(rt.lib.nm_neighbor_index_group(
+                rt.ctx, _device.ptr(voxel), ns, m, _device.ptr(counts), _device.ptr(start), _device.ptr(rows),
+                _device.ptr(tmp), tmp.numel(), rt.stream()))
+            self._group = (counts[:m], start, rows[:ns])
+        return self._group
+
+    def point_counts(self):
+        """int64 (M,): search points per voxel (np.unique's return_counts)."""
+        self._need_index("point_counts")
+        counts = self._grouping()[0]
+        return counts if self._as_torch else counts.cpu().numpy()
+
+    def members(self):
+        """(start int64[M+1], rows int64[Ns]): the rows of the search cloud voxel by voxel - voxel v holds
+        rows[start[v]:start[v+1]], ascending.  rows is np.argsort(voxel_of(search_cloud), kind="stable"),
+        the same on every run."""
+        self._need_index("members")
+        _, start, rows = self._grouping()
+        return (start, rows) if self._as_torch else (start.cpu().numpy(), rows.cpu().numpy())
+
+    def voxel_table(self, attributes, reduce="mean"):
+        """fp64 (M, D): per voxel the `reduce` ("mean", "sum", "min" or "max") of the attribute rows of the
+        search points in it.  attributes is (Ns, D) or (Ns,), 1 <= D <= 16.  "sum" adds in ascending row order
+        (np.bincount(inverse, weights=column), bit for bit), "mean" divides that sum once by the count.
+        NaN attribute values are not supported (like NaN coordinates)."""
+        self._need_index("voxel_table")
+        if reduce not in _ffi.NM_REDUCE:
+            raise ValueError("reduce must be one of 'mean', 'sum', 'min', 'max'")
+        rt = self._rt
+        attr = torch.as_tensor(attributes).to(device=rt.device, dtype=torch.float64)
+        if attr.ndim == 1:
+            attr = attr.reshape(-1, 1)
+        if attr.ndim != 2 or attr.shape[0] != self._search.shape[0]:
+            raise ValueError("attributes must have one row per search point")
+        dims = int(attr.shape[1])
+        if not 1 <= dims <= _ffi.NM_STATS_MAX_DIMS:
+            raise ValueError("between 1 and %d attribute columns per call" % _ffi.NM_STATS_MAX_DIMS)
+        attr = _unit_columns(attr)
+        _, start, rows = self._grouping()
+        m = self.n_voxels
+        table = torch.empty((m, dims), dtype=torch.float64, device=rt.device)
+        rt.check(rt.lib.nm_neighbor_index_voxel_reduce(
+            rt.ctx, _device.ptr(start), _device.ptr(rows), m, _device.ptr(attr), _device.row_stride(attr), dims,
+            _ffi.NM_REDUCE[reduce], _device.ptr(table), rt.stream()))
+        return table if isinstance(attributes, torch.Tensor) else table.cpu().numpy()
+
+    def _voxel_values(self, voxel_values):
+        """a voxel table as an fp64 device tensor (M, D) with unit column stride (a row stride is kept)"""
+        values = torch.as_tensor(voxel_values).to(device=self._rt.device, dtype=torch.float64)
+        if values.ndim == 1:
+            values = values.reshape(-1, 1)
+        if values.ndim != 2 or values.shape[0] != self.n_voxels:
+            raise ValueError("voxel_values must have one row per voxel")
+        if not 1 <= values.shape[1] <= _ffi.NM_STATS_MAX_DIMS:
+            raise ValueError("between 1 and %d attribute columns per call" % _ffi.NM_STATS_MAX_DIMS)
+        return _unit_columns(values)
+
+    def _stats_into(self, query, radius, values, count, mean, vmin, vmax, out_stride):
+        """enqueue nm_neighbor_index_stats: count (Nq,) int32 and three (Nq, D) blocks at row pitch out_stride"""
+        rt = self._rt
+        rt.check(rt.lib.nm_neighbor_index_stats(
+            rt.ctx, _device.ptr(query), query.shape[0], _device.row_stride(query),
+            ctypes.byref(self.filter.nm_lattice), float(radius), _device.ptr(self._work), self._work.numel(),
+            _device.ptr(values), _device.row_stride(values), int(values.shape[1]), _device.ptr(count), mean, vmin,
+            vmax, int(out_stride), rt.stream()))
+
+    def neighborhood_stats(self, query_cloud, radius, voxel_values):
+        """(count int32 (Nq,), mean, vmin, vmax fp64 (Nq, D)): over the voxels within `radius` of each query
+        point - the voxels lists() names - how many there are and, per column of voxel_values ((M, D) or (M,),
+        1 <= D <= 16, e.g. a voxel_table), their mean (summed in ascending voxel order, divided once by the
+        count), minimum and maximum.  no list is written.  a query point with no voxel in reach gets count 0
+        and zeros in all three tables.  NaN values are not supported (like NaN coordinates)."""
+        self._need_index("neighborhood_stats")
+        rt = self._rt
+        query = self._query_cloud(query_cloud)
+        values = self._voxel_values(voxel_values)
+        nq, dims = query.shape[0], int(values.shape[1])
+        count = torch.zeros(nq, dtype=torch.int32, device=rt.device)
+        mean, vmin, vmax = (torch.zeros((nq, dims), dtype=torch.float64, device=rt.device) for _ in range(3))
+        self._stats_into(query, radius, values, count, _device.ptr(mean), _device.ptr(vmin), _device.ptr(vmax), dims)
+        out = (count, mean, vmin, vmax)
+        return out if isinstance(query_cloud, torch.Tensor) else tuple(t.cpu().numpy() for t in out)
+
+
+def _unit_columns(table):
+    """the table itself where its rows can be walked with a row stride, else a contiguous copy"""
+    if table.shape[0] > 1 and (table.stride(1) != 1 or table.stride(0) < table.shape[1]):
+        return table.contiguous()
+    return table if table.shape[0] > 1 else table.contiguous()
 
 
 def neighbor_lists(query_cloud, search_cloud, edge_length, radius, method="auto"):
