@@ -219,6 +219,12 @@ __device__ __forceinline__ double nm_rsqrt_fast(double x)
     return y * nm_fma(hx * y, y, 1.5);
 }
 
+#ifndef NM_PAIR_CLOSED_FORM_MIN_T
+#define NM_PAIR_CLOSED_FORM_MIN_T 1e-6       // below this t the pair comes from the deflation, not from the cubic ...
+#endif
+#ifndef NM_PAIR_CLOSED_FORM_MIN_T_TOP
+#define NM_PAIR_CLOSED_FORM_MIN_T_TOP 1e-2   // ... and below this one where the pair is the two SMALL eigenvalues (see there)
+#endif
 #ifndef NM_CUBIC_NEWTON_STEPS
 #define NM_CUBIC_NEWTON_STEPS 3   // from the quadratic start: error 6.7e-4, 3.8e-7, 1.3e-13, < 1e-21 (the chord start of
                                   // round 2 - 1.3e-2 - needed four: one v_rcp_f64 and four fp64 instructions more)
@@ -260,13 +266,18 @@ __device__ __forceinline__ void nm_eig3_fast(double a00, double a01, double a02,
         const double fp = nm_fma(3.0, x2, -3.0);
         x = nm_fma(-f, __builtin_amdgcn_rcp(fp), x);
     }
-    // the other two roots of x^3 - 3x - 2r are -x/2 +- sqrt(3 (1 - x^2/4)).  with t = 1 - x^2/4
-    // formed as (2-x)(2+x)/4 (the difference is exact) an error d in x becomes d / (2 sqrt t) in the
-    // pair, so whenever the pair is not nearly double (t >= 1e-6: error < 1e-13) the closed form is as
-    // good as the deflation below and a third of its cost.  nearly all neighborhoods take it; a wave
-    // runs the deflation only when one of its lanes has a (near-)double pair.
+    // the other two roots of x^3 - 3x - 2r are -x/2 +- sqrt(3 (1 - x^2/4)), t = 1 - x^2/4 formed as
+    // (2-x)(2+x)/4 (the difference is exact).  the pair is only as good as r: an error dr in r (the roundings
+    // of the scaled determinant, up to ~4 eps) moves the two pair roots by -+ dr / (3 sqrt(3t)), i.e. by
+    // dr / (9 sqrt(3t)) of the trace (p <= tr/3): 64 dr at t = 1e-6 (measured: 4e-14 on lattice neighborhoods
+    // with 1e-6 <= t < 1e-4), below 0.65 dr from t = 1e-2 on.
+    // r < 0, the pair is l0 and l1: the two errors cancel in l0 + l1 = 2q + p x, so a planar neighborhood keeps
+    // l0 + l1 = 1 to rounding, and 1e-13 on each holds down to t = 1e-6.
+    // r >= 0, the pair is l1 and l2: l0 + l1 carries l1's error alone - 1 + 1.6e-15 on an exactly planar
+    // neighborhood at t = 3e-4, where LAPACK gives 1 to the bit - so the closed form is taken from t = 1e-2 on.
+    // below these the deflation; a wave runs it only when one of its lanes needs it.
     const double t = (2.0 - x) * (2.0 + x) * 0.25;
-    if (__builtin_expect(t >= 1e-6, 1)) {
+    if (__builtin_expect(t >= (top ? NM_PAIR_CLOSED_FORM_MIN_T_TOP : NM_PAIR_CLOSED_FORM_MIN_T), 1)) {
         const double t3 = 3.0 * t;
         const double s3 = t3 * nm_rsqrt_fast(t3);
         const double h = 0.5 * x;
@@ -427,7 +438,11 @@ __device__ __forceinline__ void nm_normal_from_moments(
     vx *= s * gx;
     vy *= s * gy;
     vz *= s * gz;
-    const bool flip = vz < 0.0 || (vz == 0.0 && (vy < 0.0 || (vy == 0.0 && vx < 0.0)));
+    // "last non-zero component positive": a component that is zero in exact arithmetic (the z of a wall's normal)
+    // comes out as rounding noise of either sign, some 1e-16 over the eigenvalue gap, and must not decide the
+    // orientation - below 1e-12, the accuracy of the vector itself, a component counts as zero
+    const double tiny = 1e-12;
+    const bool flip = vz < -tiny || (!(vz > tiny) && (vy < -tiny || (!(vy > tiny) && vx < 0.0)));
     v[0] = flip ? -vx : vx;
     v[1] = flip ? -vy : vy;
     v[2] = flip ? -vz : vz;
