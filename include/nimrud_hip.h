@@ -322,6 +322,36 @@ int nm_neighbor_index_stats(nm_ctx* ctx, const double* d_query, int64_t n_query,
                             const double* d_values, int64_t value_stride, int32_t dims, int32_t* d_count,
                             double* d_mean, double* d_min, double* d_max, int64_t out_stride, void* stream);
 
+/* ---- the k nearest voxels on the neighbor index (new symbols only: additive within ABI 7) ---------------------
+ * what cKDTree(search_voxels).query(points, k, distance_upper_bound) gave (the tree of multiscale.py:87), read
+ * off the index: no tree, nothing sorted.
+ *   candidates: for a query point all M occupied voxels of the lattice.  a voxel's squared distance is formed as
+ *     nm_neighbor_index_lists forms it: the centre (cell * e + min_corner) + e * 0.5, then
+ *     ((dx*dx + dy*dy) + dz*dz) in fp64, nothing fused.
+ *   order: by (d2, voxel index) ascending; the voxel index is the position in nm_neighbor_index_addresses, so
+ *     equal squared distances are broken by the smaller address.  (scipy leaves ties unspecified.)
+ *   limit: a voxel qualifies when d2 <= fl(max_distance * max_distance) - inclusive, like the lists (scipy's
+ *     distance_upper_bound is exclusive).  INFINITY: no limit.
+ *   output: row q has k slots, d_dist2[q * out_stride + j] and d_index[q * out_stride + j]: the first
+ *     min(k, qualifying) voxels in that order, then d2 = +infinity and index = -1 (scipy: M) in the unused
+ *     slots; columns from k on are not touched.  d_found[q] (may be NULL) = the number of real slots.  either
+ *     of d_dist2 / d_index may be NULL, not both.
+ *   query points may lie anywhere, outside the lattice too; NaN coordinates are not supported.  the result is a
+ *     function of (index, query point, k, max_distance) alone - not of the launch, of the stage that answered,
+ *     or of the other queries - and the same bit for bit on every run; rows are in the caller's order.
+ *   d_tmp: nm_neighbor_index_nearest_workspace_bytes(n_query) bytes of scratch (the queries the first stage
+ *     hands to the second); n_query < 2^31.  not needed for n_query == 0, which is NM_OK and does nothing.
+ *   errors, all before anything is queued: NM_ERR_INVALID for k outside [1, NM_NEAREST_MAX_K], out_stride < k,
+ *     a negative or NaN max_distance, bad pointers, too small a d_tmp; NM_ERR_RADIUS for a finite max_distance
+ *     beyond the ratio nm_neighbor_index_lists accepts; NM_ERR_WORKSPACE / NM_ERR_LATTICE as every entry point
+ *     that takes the index.                                                                                  */
+#define NM_NEAREST_MAX_K 32
+size_t nm_neighbor_index_nearest_workspace_bytes(int64_t n_query);
+int nm_neighbor_index_nearest(nm_ctx* ctx, const double* d_query, int64_t n_query, int64_t query_stride,
+                              const nm_lattice* lat, int32_t k, double max_distance, const void* d_work,
+                              size_t work_bytes, double* d_dist2, int64_t* d_index, int64_t out_stride,
+                              int32_t* d_found, void* d_tmp, size_t tmp_bytes, void* stream);
+
 /* ---- explicit neighborhoods -----------------------------------------------------------------------
  * features.population / centroid / pca (features.py:21-57) for a batch of explicit neighborhoods
  * given as CSR over a point array: neighborhood b is d_points[d_offsets[b] .. d_offsets[b+1]) (rows

@@ -23,6 +23,7 @@ NM_COMM_ID_BYTES = 128
 
 ABI_VERSION = 7
 NM_STATS_MAX_DIMS = 16
+NM_NEAREST_MAX_K = 32
 NM_REDUCE = {"mean": 0, "sum": 1, "min": 2, "max": 3}      # NM_REDUCE_MEAN .. NM_REDUCE_MAX
 
 c_i64 = ctypes.c_int64
@@ -115,6 +116,10 @@ SIGNATURES = {
     "nm_neighbor_index_stats": (ctypes.c_int,
                                 [c_ptr, c_ptr, c_i64, c_i64, _LATP, c_f64, c_ptr, c_size, c_ptr, c_i64, c_i32,
                                  c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
+    "nm_neighbor_index_nearest_workspace_bytes": (c_size, [c_i64]),
+    "nm_neighbor_index_nearest": (ctypes.c_int,
+                                  [c_ptr, c_ptr, c_i64, c_i64, _LATP, c_i32, c_f64, c_ptr, c_size, c_ptr, c_ptr,
+                                   c_i64, c_ptr, c_ptr, c_size, c_ptr]),
     "nm_neighborhood_features": (ctypes.c_int,
                                  [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
     "nm_halo_count": (ctypes.c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_i32, c_i32, c_ptr, c_ptr]),

@@ -619,6 +619,249 @@ __global__ __launch_bounds__(256) void k_nbr_stats(const double* __restrict__ qu
         }
 }
 
+// ---- nearest: the k nearest occupied voxels of any point --------------------------------------------------------------
+// one lane per query.  candidates are all M occupied voxels; a voxel's d2 is nbr_walk's ((dx*dx + dy*dy) + dz*dz)
+// on nm_centre, voxels are ordered by (d2, voxel index) and a voxel qualifies when d2 <= r2 (NaN fails).
+//
+// the search examines cubes of growing half-width S around the clamped home cell h, shell by shell (the cells of
+// cube S1 that are not in cube S0), and keeps the k best of everything it has examined.  after the cube of
+// half-width S has been examined completely the list is FINAL when one of these holds:
+//   (a) it holds k voxels and the k-th d2 is <= ((S + 1/2 - 1e-6) * e)^2.  the query lies in its home cell, so a
+//       cell whose offset from h exceeds S on some axis has its centre more than (S + 1/2) * e away on that axis:
+//       every cell outside the cube is strictly farther than the k-th voxel and cannot enter the list, not even
+//       through the tie rule.  the 1e-6 margin (far above the rounding of the cell division and the centres)
+//       keeps the comparison strict.  a query outside the lattice has its home cell clamped towards the lattice;
+//       the cells beyond the cube then lie on the inner side only, where the query is at least as far from them
+//       as a point of the clamped home cell would be.  (the bound k_knn_fallback uses.)
+//   (b) S has reached the candidate window of the limit, nbr_candidate_width(max_distance, e): no cell outside
+//       it holds a voxel within the limit - the window lists() walks.
+//   (c) the cube covers the lattice: there is no cell outside.
+// which S values are stepped through, and which kernel answers, changes the work and never the answer: the k
+// smallest of a total order over a set that provably contains them.
+//
+// best list: K slots in registers (K = the compile-time bucket k falls in), sorted ascending, the fallback's
+// branch-free insertion.  k < K uses the LAST k slots: the first K - k hold -infinity, which no candidate
+// precedes, so the k-th best is always bd[K - 1] - no search for slot k - 1.  the tie key is the voxel index
+// itself (rank[word] + popc(word below the bit)): it is the output, it is 32 bits whatever the cube's width (a
+// cell-offset code needs 64 beyond +-511 cells, and the wide stage goes far beyond), and it does not depend on
+// the home cell.  its rank word is loaded only for a word with a candidate that can enter the list.
+//
+// stages: k_nn_near takes every query up to cubes of half-width NN_NEAR_CAP.  a query that is not final by then
+// is appended to a list in the caller's scratch (one atomic per wave) with the half-width it needs next, and
+// k_nn_wide - one lane per LISTED query, so no finished lane waits - starts it again from that cube.  the wide
+// stage skips empty space through the scanned totals[]: the occupied cells of any run of consecutive pieces (a
+// piece = 2^chunk_log2 leaves of one lattice row) is the difference of two entries, M closing the last; it asks
+// that per z-layer of the cube (all rows of the layer in the y-range, a superset), per row and per piece before
+// it reads a leaf word.
+constexpr int NN_NEAR_CAP = 8;
+constexpr size_t NN_HEADER_BYTES = 256;          // word 0: number of listed queries
+
+struct NnArgs {
+    const double* query;
+    int64_t nq, qstride;
+    const uint32_t* leaf;
+    const uint32_t* rank;
+    const uint32_t* totals;      // scanned
+    const uint32_t* header;      // [0] M
+    LatticeDev L;
+    int32_t chunk_log2, piece_bits;
+    int64_t n_totals;
+    int32_t k;
+    int32_t s_limit;             // half-width of the limit's window, -1: no limit
+    double r2;
+    double* dist2;
+    int64_t* index;
+    int64_t ostride;
+    int32_t* found;
+    uint32_t* pend_count;
+    uint2* pend;                 // {query, half-width to start from}
+};
+
+// occupied cells before piece i of the address order
+__device__ __forceinline__ uint32_t nn_before(const NnArgs& A, uint32_t m, int64_t i)
+{
+    return i < A.n_totals ? A.totals[i] : m;
+}
+
+// searches query q from a full cube of half-width s_first on.  true: final, the row is written.  false: the
+// next cube would be wider than `cap`; *hint is its half-width and nothing is written
+template <int K, bool WIDE>
+__device__ __forceinline__ bool nn_search(const NnArgs& A, int64_t q, int64_t s_first, int64_t cap, uint32_t* hint)
+{
+    const LatticeDev& L = A.L;
+    const double* p = A.query + q * A.qstride;
+    const double qx = p[0], qy = p[1], qz = p[2];
+    const int32_t hx = nm_clamp_cell(nm_cell_f(qx, L.min_x, L.edge));
+    const int32_t hy = nm_clamp_cell(nm_cell_f(qy, L.min_y, L.edge));
+    const int32_t hz = nm_clamp_cell(nm_cell_f(qz, L.min_z, L.edge));
+    const int32_t nx = (1 << L.wx) - 1, ny = (1 << L.wy) - 1, nz = (1 << L.wz) - 1;      // last cells
+    // (c): the half-width at which the cube covers the lattice; (b): the limit's window
+    int64_t s_end = max(max((int64_t)hx, (int64_t)nx - hx), max((int64_t)hy, (int64_t)ny - hy));
+    s_end = max(s_end, max((int64_t)hz, (int64_t)nz - hz));
+    if (A.s_limit >= 0 && A.s_limit < s_end) s_end = A.s_limit;
+    const uint32_t m = WIDE ? A.header[0] : 0u;
+    const int32_t pshift = NM_SBX_BITS + A.chunk_log2;
+
+    double bd[K];
+    uint32_t bi[K];
+#pragma unroll
+    for (int t = 0; t < K; ++t) {
+        const bool real = t >= K - A.k;
+        bd[t] = real ? INFINITY : -INFINITY;
+        bi[t] = real ? 0xFFFFFFFFu : 0u;
+    }
+    double cut = A.r2;       // min(r2, k-th best): a candidate beyond it neither qualifies nor enters the list
+    int64_t S0 = -1, S1 = min(s_first, s_end);
+    for (;;) {
+        // the shell: cube S1 clipped to the lattice, without cube S0 (S0 = -1: nothing was examined yet)
+        const int32_t X0 = (int32_t)max((int64_t)hx - S1, (int64_t)0), X1 = (int32_t)min((int64_t)hx + S1, (int64_t)nx);
+        const int32_t Y0 = (int32_t)max((int64_t)hy - S1, (int64_t)0), Y1 = (int32_t)min((int64_t)hy + S1, (int64_t)ny);
+        const int32_t Z0 = (int32_t)max((int64_t)hz - S1, (int64_t)0), Z1 = (int32_t)min((int64_t)hz + S1, (int64_t)nz);
+        if (X0 <= X1 && Y0 <= Y1) {
+            for (int32_t gz = Z0; gz <= Z1; ++gz) {
+                double d = qz - nm_centre(gz, L.min_z, L.edge, L.half_edge);
+                const double dz2 = d * d;
+                // as nbr_walk's row skip: d2 >= fl(dy2 + dz2) >= dz2 by monotonic rounding
+                if (!(dz2 <= cut)) continue;
+                const bool inz = (int64_t)gz >= hz - S0 && (int64_t)gz <= hz + S0;
+                const int64_t layer = (int64_t)gz << (L.by + NM_SBY_BITS);
+                if (WIDE) {
+                    const int64_t a = (layer | Y0) << A.piece_bits, b = ((layer | Y1) + 1) << A.piece_bits;
+                    if (nn_before(A, m, b) == nn_before(A, m, a)) continue;
+                }
+                for (int32_t gy = Y0; gy <= Y1; ++gy) {
+                    d = qy - nm_centre(gy, L.min_y, L.edge, L.half_edge);
+                    const double dy2 = d * d;
+                    if (!(dy2 + dz2 <= cut)) continue;
+                    const bool inner = inz && (int64_t)gy >= hy - S0 && (int64_t)gy <= hy + S0;
+                    const uint32_t wrow = (((uint32_t)gz & 7u) << 3) | ((uint32_t)gy & 7u);
+                    const int64_t row = (layer | gy) << A.piece_bits;
+                    // a row that crosses the examined cube has a piece on either side of it
+                    for (int seg = 0; seg < (inner ? 2 : 1); ++seg) {
+                        int32_t xa = X0, xb = X1;
+                        if (inner) {
+                            if (seg == 0) xb = (int32_t)min((int64_t)X1, (int64_t)hx - S0 - 1);
+                            else xa = (int32_t)max((int64_t)X0, (int64_t)hx + S0 + 1);
+                        }
+                        if (xa > xb) continue;
+                        int32_t piece_seen = -1;
+                        if (WIDE) {
+                            const int32_t pa = xa >> pshift, pb = xb >> pshift;
+                            if (nn_before(A, m, row + pb + 1) == nn_before(A, m, row + pa)) continue;
+                            if (pa == pb) piece_seen = pa;
+                        }
+                        for (int32_t sbx = xa >> NM_SBX_BITS; sbx <= (xb >> NM_SBX_BITS); ++sbx) {
+                            if (WIDE) {
+                                const int32_t pc = sbx >> A.chunk_log2;
+                                if (pc != piece_seen) {
+                                    piece_seen = pc;
+                                    if (nn_before(A, m, row + pc + 1) == nn_before(A, m, row + pc)) {
+                                        sbx = ((pc + 1) << A.chunk_log2) - 1;
+                                        continue;
+                                    }
+                                }
+                            }
+                            const uint64_t at = nm_sb_key((uint32_t)sbx, (uint32_t)gy >> NM_SBY_BITS,
+                                                          (uint32_t)gz >> NM_SBZ_BITS, L) * NM_LEAF_WORDS + wrow;
+                            const uint32_t all = A.leaf[at];
+                            const int32_t base = sbx << NM_SBX_BITS;
+                            const int32_t lo = max(xa - base, 0), hi = min(xb - base, 31);
+                            uint32_t word = all & (0xFFFFFFFFu >> (31 - hi)) & (0xFFFFFFFFu << lo);
+                            uint32_t r0 = 0;
+                            bool have_rank = false;
+                            while (word) {
+                                const int bit = __ffs((int)word) - 1;
+                                word &= word - 1u;
+                                d = qx - nm_centre(base + bit, L.min_x, L.edge, L.half_edge);
+                                double cd = (d * d + dy2) + dz2;
+                                if (!(cd <= cut)) continue;
+                                if (!have_rank) {
+                                    r0 = A.rank[at];
+                                    have_rank = true;
+                                }
+                                uint32_t ci = r0 + (uint32_t)__popc(all & ((1u << bit) - 1u));
+#pragma unroll
+                                for (int t = 0; t < K; ++t) {
+                                    const bool before = cd < bd[t] || (cd == bd[t] && ci < bi[t]);
+                                    const double td = before ? bd[t] : cd;
+                                    const uint32_t ti = before ? bi[t] : ci;
+                                    bd[t] = before ? cd : bd[t];
+                                    bi[t] = before ? ci : bi[t];
+                                    cd = td;
+                                    ci = ti;
+                                }
+                                cut = bd[K - 1] < A.r2 ? bd[K - 1] : A.r2;
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        const double kth = bd[K - 1];
+        if (S1 >= s_end) break;                                   // (b), (c)
+        const double reach = ((double)S1 + 0.5 - 1e-6) * L.edge;
+        if (kth <= reach * reach) break;                          // (a)
+        // the next cube: with k voxels in hand the smallest whose bound (a) covers the k-th (it can only come
+        // closer, so that cube is the last); else twice as wide.  only the test above decides what is final
+        int64_t next = 2 * S1 > 0 ? 2 * S1 : 1;
+        if (kth < INFINITY) {
+            next = (int64_t)ceil(sqrt(kth) / L.edge - 0.5 + 1e-6);
+            if (next <= S1) next = S1 + 1;
+        }
+        if (next > s_end) next = s_end;
+        if (next > cap) {
+            *hint = (uint32_t)next;
+            return false;
+        }
+        S0 = S1;
+        S1 = next;
+    }
+    int32_t n = 0;
+#pragma unroll
+    for (int t = 0; t < K; ++t) {
+        const int j = t - (K - A.k);
+        if (j >= 0) {
+            const bool real = bi[t] != 0xFFFFFFFFu;
+            n += real;
+            if (A.dist2) A.dist2[q * A.ostride + j] = bd[t];          // (+infinity where no voxel is)
+            if (A.index) A.index[q * A.ostride + j] = real ? (int64_t)bi[t] : (int64_t)-1;
+        }
+    }
+    if (A.found) A.found[q] = n;
+    return true;
+}
+
+// the first cube holds at least k cells: 27 at half-width 1, 125 at 2 (k <= NM_NEAREST_MAX_K = 32)
+__device__ __forceinline__ int64_t nn_first_cube(int32_t k) { return k <= 27 ? 1 : 2; }
+
+template <int K>
+__global__ __launch_bounds__(256) void k_nn_near(NnArgs A)
+{
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool pending = false;
+    uint32_t hint = 0;
+    if (q < A.nq) pending = !nn_search<K, false>(A, q, nn_first_cube(A.k), NN_NEAR_CAP, &hint);
+    // the wave's unfinished queries take consecutive places of the list (their order in it decides nothing)
+    const unsigned long long mask = __ballot(pending);
+    if (!mask) return;
+    const int lane = threadIdx.x & 63;
+    uint32_t base = 0;
+    if (lane == __ffsll((long long)mask) - 1) base = atomicAdd(A.pend_count, (uint32_t)__popcll(mask));
+    base = __shfl(base, __ffsll((long long)mask) - 1);
+    if (pending) A.pend[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = make_uint2((uint32_t)q, hint);
+}
+
+// one wave per block: the listed queries are spread over the device; the blocks beyond the list leave at once
+template <int K>
+__global__ __launch_bounds__(64) void k_nn_wide(NnArgs A)
+{
+    const int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (at >= (int64_t)*A.pend_count) return;
+    const uint2 e = A.pend[at];
+    uint32_t hint = 0;
+    nn_search<K, true>(A, (int64_t)e.x, (int64_t)e.y, INT64_MAX, &hint);
+}
+
 // argument checks shared by the entry points that take a built workspace
 int nbr_check_index(nm_ctx* ctx, const char* who, const nm_lattice* lat, const void* d_work, size_t work_bytes,
                     LatticeDev* L, NbrPlan* P)
@@ -848,6 +1091,84 @@ extern "C" int nm_neighbor_index_stats(nm_ctx* ctx, const double* d_query, int64
     else if (dims <= 4) NM_STATS_LAUNCH(4);
     else NM_STATS_LAUNCH(16);
 #undef NM_STATS_LAUNCH
+    NM_HIP(ctx, hipGetLastError());
+    return NM_OK;
+}
+
+// ---- nearest voxels on the index (additive within ABI 7) ----------------------------------------------------------------
+
+extern "C" size_t nm_neighbor_index_nearest_workspace_bytes(int64_t n_query)
+{
+    if (n_query < 0 || n_query >= (int64_t)1 << 31) return 0;
+    return NN_HEADER_BYTES + ((size_t)n_query * sizeof(uint2) + 15) / 16 * 16;
+}
+
+extern "C" int nm_neighbor_index_nearest(nm_ctx* ctx, const double* d_query, int64_t n_query, int64_t query_stride,
+                                         const nm_lattice* lat, int32_t k, double max_distance, const void* d_work,
+                                         size_t work_bytes, double* d_dist2, int64_t* d_index, int64_t out_stride,
+                                         int32_t* d_found, void* d_tmp, size_t tmp_bytes, void* stream)
+{
+    NM_ENTER_STREAM(ctx, stream);
+    if (n_query < 0 || n_query >= (int64_t)1 << 31 || query_stride < 3 || (n_query > 0 && !d_query))
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_nearest: bad arguments");
+    if (k < 1 || k > NM_NEAREST_MAX_K)
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_nearest: k = %d outside [1, %d]", k, NM_NEAREST_MAX_K);
+    if (!d_dist2 && !d_index) NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_nearest: nothing to write");
+    if (out_stride < k)
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_nearest: output stride below k");
+    if (!(max_distance >= 0.0))      // (NaN fails)
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_nearest: max_distance must be >= 0 (INFINITY: no limit)");
+    LatticeDev L;
+    NbrPlan P;
+    int rc = nbr_check_index(ctx, "nm_neighbor_index_nearest", lat, d_work, work_bytes, &L, &P);
+    if (rc) return rc;
+    int32_t s_limit = -1;
+    if (max_distance < INFINITY) {
+        int32_t dmin = 0;
+        if (nbr_candidate_width(max_distance, lat->edge, &dmin) < 0)
+            NM_FAIL(ctx, NM_ERR_RADIUS, "max_distance/edge ratio outside the supported range");
+        s_limit = -dmin;
+    }
+    if (n_query == 0) return NM_OK;
+    if (!d_tmp || tmp_bytes < nm_neighbor_index_nearest_workspace_bytes(n_query))
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_nearest: temporary workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    const char* w = (const char*)d_work;
+    NnArgs A;
+    A.query = d_query;
+    A.nq = n_query;
+    A.qstride = query_stride;
+    A.leaf = (const uint32_t*)(w + P.off_leaf);
+    A.rank = (const uint32_t*)(w + P.off_rank);
+    A.totals = (const uint32_t*)(w + P.off_totals);
+    A.header = (const uint32_t*)w;
+    A.L = L;
+    A.chunk_log2 = P.chunk_log2;
+    A.piece_bits = P.piece_bits;
+    A.n_totals = P.totals;
+    A.k = k;
+    A.s_limit = s_limit;
+    A.r2 = max_distance * max_distance;
+    A.dist2 = d_dist2;
+    A.index = d_index;
+    A.ostride = out_stride;
+    A.found = d_found;
+    A.pend_count = (uint32_t*)d_tmp;
+    A.pend = (uint2*)((char*)d_tmp + NN_HEADER_BYTES);
+    // a limit whose window the near stage reaches leaves nothing for the wide stage
+    const bool wide = s_limit < 0 || s_limit > NN_NEAR_CAP;
+    if (wide) NM_HIP(ctx, hipMemsetAsync(d_tmp, 0, NN_HEADER_BYTES, s));
+    const unsigned near_blocks = (unsigned)((n_query + 255) / 256), wide_blocks = (unsigned)((n_query + 63) / 64);
+#define NM_NEAREST_LAUNCH(K)                                         \
+    do {                                                             \
+        k_nn_near<K><<<near_blocks, 256, 0, s>>>(A);                 \
+        if (wide) k_nn_wide<K><<<wide_blocks, 64, 0, s>>>(A);        \
+    } while (0)
+    if (k == 1) NM_NEAREST_LAUNCH(1);
+    else if (k <= 8) NM_NEAREST_LAUNCH(8);
+    else if (k <= 16) NM_NEAREST_LAUNCH(16);
+    else NM_NEAREST_LAUNCH(32);
+#undef NM_NEAREST_LAUNCH
     NM_HIP(ctx, hipGetLastError());
     return NM_OK;
 }

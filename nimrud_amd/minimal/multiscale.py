@@ -293,8 +293,10 @@ class NeighborIndex(object):
         .voxel_table(attributes, reduce="mean")   per-voxel mean / sum / min / max of per-point columns
         .neighborhood_stats(query_cloud, radius, voxel_values) -> (count, mean, vmin, vmax) per query point
                                 over the voxels lists() would name, without writing the lists
+        .nearest(query_cloud, k, max_distance=None) -> (distance (Nq, k), index (Nq, k)): the k nearest voxels
+                                of every query point (cKDTree(voxels()).query), ties by the smaller position
     torch in, torch out; numpy in, numpy out (addresses / voxels / point_counts / members follow the search
-    cloud, lists / neighborhood_stats the query cloud, voxel_of and voxel_table their argument)."""
+    cloud, lists / neighborhood_stats / nearest the query cloud, voxel_of and voxel_table their argument)."""
 
     def __init__(self, search_cloud, edge_length, method="auto"):
         if method not in ("auto", "index", "search"):
@@ -520,6 +522,50 @@ class NeighborIndex(object):
         out = (count, mean, vmin, vmax)
         return out if isinstance(query_cloud, torch.Tensor) else tuple(t.cpu().numpy() for t in out)
 
+    def _nearest_device(self, query, k, max_distance):
+        """enqueue nm_neighbor_index_nearest: (d2 fp64 (Nq, k), index int64 (Nq, k), found int32 (Nq,))"""
+        rt = self._rt
+        nq = query.shape[0]
+        dist2 = torch.empty((nq, k), dtype=torch.float64, device=rt.device)
+        index = torch.empty((nq, k), dtype=torch.int64, device=rt.device)
+        found = torch.empty(nq, dtype=torch.int32, device=rt.device)
+        if nq == 0:
+            return dist2, index, found
+        tmp = rt.workspace(rt.lib.nm_neighbor_index_nearest_workspace_bytes(nq))
+        rt.check(rt.lib.nm_neighbor_index_nearest(
+            rt.ctx, _device.ptr(query), nq, _device.row_stride(query), ctypes.byref(self.filter.nm_lattice), k,
+            max_distance, _device.ptr(self._work), self._work.numel(), _device.ptr(dist2), _device.ptr(index), k,
+            _device.ptr(found), _device.ptr(tmp), tmp.numel(), rt.stream()))
+        return dist2, index, found
+
+    def nearest(self, query_cloud, k, max_distance=None, squared=False):
+        """(distance fp64 (Nq, k), index int64 (Nq, k)): for every query point its k nearest occupied voxels -
+        cKDTree(voxels()).query(query_cloud, k, distance_upper_bound), the other half of the tree at
+        multiscale.py:87 - nearest first.  the squared distance to a voxel centre is formed as lists() forms it;
+        voxels are ordered by (squared distance, position in addresses() / voxels()), so equal distances are
+        broken by the smaller position (scipy leaves ties unspecified).  with `max_distance` only voxels with
+        d2 <= max_distance * max_distance count: inclusive, like lists() (scipy's distance_upper_bound is
+        exclusive); None is no limit.  a row with fewer than k such voxels ends in distance inf and index -1,
+        the handle's "none" as in voxel_of (scipy writes M there).  always 2-D, also for k = 1 (scipy squeezes).
+        1 <= k <= 32.  distance is torch.sqrt of the squared distance, or that itself with squared=True.  query
+        points may lie anywhere, outside the lattice too; the search cloud passed by identity is not uploaded
+        again."""
+        self._need_index("nearest")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise ValueError("k must be an integer")
+        k = int(k)
+        if not 1 <= k <= _ffi.NM_NEAREST_MAX_K:
+            raise ValueError("k must lie in [1, %d]" % _ffi.NM_NEAREST_MAX_K)
+        limit = float("inf") if max_distance is None else float(max_distance)
+        if not limit >= 0.0:
+            raise ValueError("max_distance must be a number >= 0 (None: no limit)")
+        query = self._query_cloud(query_cloud)
+        dist2, index, _ = self._nearest_device(query, k, limit)
+        distance = dist2 if squared else torch.sqrt(dist2)
+        if isinstance(query_cloud, torch.Tensor):
+            return distance, index
+        return distance.cpu().numpy(), index.cpu().numpy()
+
 
 def _unit_columns(table):
     """the table itself where its rows can be walked with a row stride, else a contiguous copy"""
@@ -539,3 +585,11 @@ def neighbor_lists(query_cloud, search_cloud, edge_length, radius, method="auto"
     hundred times slower per point-scale than the fused feature path); "index" raises ValueError when the
     lattice is out of range.  the results are identical."""
     return NeighborIndex(search_cloud, edge_length, method=method).lists(query_cloud, radius)
+
+
+def nearest_voxels(query_cloud, search_cloud, edge_length, k, max_distance=None):
+    """(distance fp64 (Nq, k), index int64 (Nq, k)): the k nearest voxels of VoxelFilter.unique_voxels(
+    search_cloud) for every query point, what cKDTree(search_voxels).query(query_cloud, k) gives on the tree of
+    multiscale.py:87 - see NeighborIndex.nearest for order, ties, limit and padding.  one NeighborIndex (method
+    "index"), built and asked once - keep the handle yourself to ask again."""
+    return NeighborIndex(search_cloud, edge_length, method="index").nearest(query_cloud, k, max_distance)
