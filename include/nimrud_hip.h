@@ -352,6 +352,33 @@ int nm_neighbor_index_nearest(nm_ctx* ctx, const double* d_query, int64_t n_quer
                               size_t work_bytes, double* d_dist2, int64_t* d_index, int64_t out_stride,
                               int32_t* d_found, void* d_tmp, size_t tmp_bytes, void* stream);
 
+/* ---- connected components of the voxel graph on the neighbor index (new symbols only: additive within ABI 7) --
+ * Euclidean cluster extraction: "the voxels that can be reached from here in steps of at most `radius`".  no edge
+ * list is written; every voxel walks the forward half of its window once and joins what it finds in a lock-free
+ * union-find (no lane ever waits for another).
+ *   vertices: the M occupied voxels, named by their position in nm_neighbor_index_addresses.
+ *   edges: u ~ v iff nm_neighbor_index_lists, asked with the voxel centres as queries, names v for u (or u for v):
+ *     same home cell, window, row skip and test ((dx*dx + dy*dy) + dz*dz) <= r*r, inclusive.
+ *   d_class (int64[M], may be NULL = one class): a negative class takes the voxel out of the graph; an edge joins
+ *     voxels of EQUAL class only, so every class is segmented by the one call.
+ *   d_weight (int64[M], may be NULL = 1 each): a component's size is the sum of its weights (e.g. points per voxel).
+ *   min_size: components of a smaller size are dropped.
+ *   output: d_label[M] = the component of every voxel, -1 for voxels outside the graph and for dropped components;
+ *     d_size[c] = the size of component c (room for M entries); d_count (int64[2]) = {C = components kept,
+ *     components before min_size}.  kept components are numbered 0..C-1 in ascending order of their smallest voxel
+ *     position.  sizes are integer sums: the result is a function of the arguments alone, bit for bit on every run.
+ *   d_tmp: nm_neighbor_index_components_workspace_bytes(M) bytes (16-byte aligned); the query needs no GPU, is
+ *     monotone in M and 0 for M < 0 or M >= 2^31.  M itself is known on the device only: a d_tmp that takes the
+ *     minimum (the query at 0) but not this index's M labels nothing and sets d_count to {-1, -1}.
+ *   errors, all before anything is queued: NM_ERR_INVALID for a null output or lattice, NM_ERR_RADIUS for a NaN or
+ *     negative radius and as nm_neighbor_index_lists, NM_ERR_WORKSPACE for too small a d_work or a d_tmp below the
+ *     minimum, NM_ERR_LATTICE as every entry point that takes the index.  nothing here waits for the device.      */
+size_t nm_neighbor_index_components_workspace_bytes(int64_t n_voxels);
+int nm_neighbor_index_components(nm_ctx* ctx, const nm_lattice* lat, double radius, const void* d_work,
+                                 size_t work_bytes, const int64_t* d_class, const int64_t* d_weight,
+                                 int64_t min_size, int64_t* d_label, int64_t* d_size, int64_t* d_count,
+                                 void* d_tmp, size_t tmp_bytes, void* stream);
+
 /* ---- explicit neighborhoods -----------------------------------------------------------------------
  * features.population / centroid / pca (features.py:21-57) for a batch of explicit neighborhoods
  * given as CSR over a point array: neighborhood b is d_points[d_offsets[b] .. d_offsets[b+1]) (rows

@@ -120,6 +120,10 @@ SIGNATURES = {
     "nm_neighbor_index_nearest": (ctypes.c_int,
                                   [c_ptr, c_ptr, c_i64, c_i64, _LATP, c_i32, c_f64, c_ptr, c_size, c_ptr, c_ptr,
                                    c_i64, c_ptr, c_ptr, c_size, c_ptr]),
+    "nm_neighbor_index_components_workspace_bytes": (c_size, [c_i64]),
+    "nm_neighbor_index_components": (ctypes.c_int,
+                                     [c_ptr, _LATP, c_f64, c_ptr, c_size, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr,
+                                      c_ptr, c_size, c_ptr]),
     "nm_neighborhood_features": (ctypes.c_int,
                                  [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
     "nm_halo_count": (ctypes.c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_i32, c_i32, c_ptr, c_ptr]),

@@ -7,6 +7,7 @@
 // for any number of query clouds and radii: no sort, no address array, no search.
 // on the same index, attributes: the voxel of a point (np.unique's inverse), the rows of every voxel, per-voxel
 // reductions of per-point columns, and per-neighborhood count / mean / min / max of a voxel table without a list.
+// and the graph itself: the connected components of the voxels under "within r", by a lock-free union-find.
 //
 // workspace (nm_neighbor_index_workspace_bytes), S = superblocks of the lattice (at most 2^NM_DENSE_LOG2):
 //   header  256 B      [0] M, written by the scan
@@ -268,13 +269,13 @@ __global__ __launch_bounds__(NBR_SCAN_THREADS) void k_nbr_scan_apply(uint32_t* _
 __global__ __launch_bounds__(256) void k_nbr_addresses(const uint32_t* __restrict__ leaf,
                                                        const uint32_t* __restrict__ rank,
                                                        const uint32_t* __restrict__ header, LatticeDev L,
-                                                       uint64_t words, int64_t* __restrict__ out)
+                                                       uint64_t words, int64_t* __restrict__ out, uint32_t room)
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= words) return;
     uint32_t word = leaf[i];
     if (!word) return;
-    const uint32_t m = header[0];
+    const uint32_t m = min(header[0], room);       // (room: entries `out` has; the caller's promise, or a scratch's size)
     const uint64_t sb = i >> (NM_SBY_BITS + NM_SBZ_BITS);
     const uint32_t w = (uint32_t)i & (NM_LEAF_WORDS - 1);
     const int64_t sby = (int64_t)(sb & ((1ull << L.by) - 1ull));
@@ -862,6 +863,330 @@ __global__ __launch_bounds__(64) void k_nn_wide(NnArgs A)
     nn_search<K, true>(A, (int64_t)e.x, (int64_t)e.y, INT64_MAX, &hint);
 }
 
+// ---- components: the connected components of the voxel graph ------------------------------------------------------------
+// vertices: the M occupied voxels by position; u ~ v iff v is in lists(voxels(), r)[u] (or the other way round:
+// for a voxel centre as query the home cell is the voxel's own cell, the window is symmetric about it, and
+// ((dx*dx + dy2) + dz2) has the same value from either end, so the relation is symmetric as computed) and both carry
+// the same class >= 0.  no list is written: every voxel walks the FORWARD half of its window - the cells of a larger
+// address, i.e. the voxels of a larger position - so every edge is seen once, from its smaller end, and is handed to
+// a lock-free union-find.
+//
+// union-find: parent[x] <= x always (only a root is ever hooked, under a smaller node, by compare-and-swap on its
+// own word; path halving replaces a parent by the parent's parent, smaller still), so walks strictly descend, end,
+// and the root of a finished tree is the smallest position of its component - whatever order the lanes ran in.
+// nobody waits: a failed compare-and-swap returns the word another lane wrote, and the loop goes on from THAT node,
+// strictly below the one it tried; there is no value a lane polls for.  parent[] is read and written with relaxed
+// device-scope atomics while lanes race (link, flatten); a stale read is an older parent, still in the same tree.
+//
+// tmp (nm_neighbor_index_components_workspace_bytes), room = the voxel count rounded up to whole scan tiles:
+//   header  256 B      word 0: components kept (the scan's total)
+//   partial 8 KB       the scan's per-block sums
+//   addr    room * 8   the address of every voxel (k_nbr_addresses): the lane of voxel v finds its cell there
+//   size    room * 8   per ROOT the sum of its component's weights (integer atomics: exact in any order)
+//   parent  room * 4   the forest; CC_NONE for a voxel that is not in the graph
+//   keep    room * 4   1 for the root of a kept component, then (scanned in place) its number
+constexpr uint32_t CC_NONE = 0xFFFFFFFFu;
+
+struct CcPlan {
+    int64_t room;
+    int32_t scan_blocks, tiles_per_block;
+    size_t off_partial, off_addr, off_size, off_parent, off_keep, bytes;
+};
+
+CcPlan cc_plan_tiles(int64_t tiles)
+{
+    CcPlan C;
+    C.room = tiles * NBR_SCAN_TILE;
+    C.scan_blocks = (int32_t)(tiles < NBR_SCAN_MAX_BLOCKS ? tiles : NBR_SCAN_MAX_BLOCKS);
+    C.tiles_per_block = (int32_t)((tiles + C.scan_blocks - 1) / C.scan_blocks);
+    C.off_partial = NBR_HEADER_BYTES;
+    C.off_addr = C.off_partial + (size_t)NBR_SCAN_MAX_BLOCKS * 4;
+    C.off_size = C.off_addr + (size_t)C.room * 8;
+    C.off_parent = C.off_size + (size_t)C.room * 8;
+    C.off_keep = C.off_parent + (size_t)C.room * 4;
+    C.bytes = C.off_keep + (size_t)C.room * 4;
+    return C;
+}
+
+CcPlan cc_plan(int64_t n) { return cc_plan_tiles(n > 0 ? (n + NBR_SCAN_TILE - 1) / NBR_SCAN_TILE : 1); }
+
+// the plan a scratch of `bytes` has room for (at least cc_plan(0).bytes; M itself is known on the device only)
+CcPlan cc_plan_of(size_t bytes)
+{
+    const size_t fixed = cc_plan(0).bytes - (size_t)NBR_SCAN_TILE * 24;
+    int64_t tiles = (int64_t)((bytes - fixed) / ((size_t)NBR_SCAN_TILE * 24));
+    const int64_t most = ((int64_t)1 << 31) / NBR_SCAN_TILE;          // positions are 32 bits, M < 2^31
+    return cc_plan_tiles(tiles < most ? tiles : most);
+}
+
+// M as the kernels take it: nothing at all where the scratch has no room for it (k_cc_label reports that)
+__device__ __forceinline__ uint32_t cc_voxels(const uint32_t* __restrict__ index_header, uint32_t room)
+{
+    const uint32_t m = index_header[0];
+    return m <= room ? m : 0u;
+}
+
+__device__ __forceinline__ uint32_t cc_load(uint32_t* p)
+{
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ void cc_store(uint32_t* p, uint32_t x)
+{
+    __hip_atomic_store(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the root of x's tree as of some moment of the walk, halving the path on the way.  x strictly descends
+__device__ __forceinline__ uint32_t cc_find(uint32_t* parent, uint32_t x)
+{
+    uint32_t p = cc_load(parent + x);
+    while (p != x) {
+        const uint32_t g = cc_load(parent + p);
+        if (g == p) return p;
+        cc_store(parent + x, g);       // x is no root and never will be again: no compare-and-swap can want this word
+        x = g;
+        p = cc_load(parent + x);
+    }
+    return x;
+}
+
+// the root of x's tree once nobody links any more, nothing written: in k_cc_flatten only the lane of voxel v stores
+// parent[v], and what it stores is final (a halving store of another lane could land behind it and undo it)
+__device__ __forceinline__ uint32_t cc_root(uint32_t* parent, uint32_t x)
+{
+    uint32_t p = cc_load(parent + x);
+    while (p != x) {
+        x = p;
+        p = cc_load(parent + x);
+    }
+    return x;
+}
+
+// joins u's tree to the tree `mine` is in (mine: the root of the lane's own tree when the lane last looked); returns
+// a node of the joined tree no larger than either root found.  the walk up from u stops as soon as it meets `mine`:
+// u hangs below it, the trees are one, and the root's word - the one word every lane of a large component would
+// otherwise load twice per edge - is not touched.  a + b strictly falls with every failed compare-and-swap, so the
+// loop ends whatever the other lanes do
+__device__ __forceinline__ uint32_t cc_join(uint32_t* parent, uint32_t mine, uint32_t u)
+{
+    uint32_t b = u;
+    uint32_t p = cc_load(parent + b);
+    while (p != b) {
+        if (p == mine) return mine;
+        const uint32_t g = cc_load(parent + p);
+        if (g == p) {
+            b = p;
+            break;
+        }
+        cc_store(parent + b, g);       // (halving, as cc_find)
+        if (g == mine) return mine;
+        b = g;
+        p = cc_load(parent + b);
+    }
+    uint32_t a = cc_find(parent, mine);
+    while (a != b) {
+        const uint32_t hi = max(a, b), lo = min(a, b);
+        const uint32_t seen = atomicCAS(parent + hi, hi, lo);
+        if (seen == hi) return lo;     // hooked (lo may have stopped being a root meanwhile: still smaller, same tree)
+        a = cc_find(parent, seen);     // someone else hooked hi, under seen < hi
+        b = lo;
+    }
+    return a;
+}
+
+// nbr_walk's sibling for a voxel (ox, oy, oz) as its own query: the same centre, home cell, clipped window, row
+// skip and unfused test, over the cells of a LARGER address only - bits above its own in its row, rows of a larger
+// gy in its layer, every row of a larger gz.  hit(voxel) in ascending voxel order, every one > the voxel's own
+template <typename F>
+__device__ __forceinline__ void nbr_walk_forward(int32_t ox, int32_t oy, int32_t oz,
+                                                 const uint32_t* __restrict__ leaf,
+                                                 const uint32_t* __restrict__ rank, const LatticeDev& L, double r2,
+                                                 int32_t dmin, int32_t W, F&& hit)
+{
+    const double qx = nm_centre(ox, L.min_x, L.edge, L.half_edge);
+    const double qy = nm_centre(oy, L.min_y, L.edge, L.half_edge);
+    const double qz = nm_centre(oz, L.min_z, L.edge, L.half_edge);
+    const int32_t hx = nm_clamp_cell(nm_cell_f(qx, L.min_x, L.edge));
+    const int32_t hy = nm_clamp_cell(nm_cell_f(qy, L.min_y, L.edge));
+    const int32_t hz = nm_clamp_cell(nm_cell_f(qz, L.min_z, L.edge));
+    const int32_t x0 = max(hx + dmin, 0), x1 = min(hx + dmin + W - 1, (1 << L.wx) - 1);
+    const int32_t y0 = max(hy + dmin, 0), y1 = min(hy + dmin + W - 1, (1 << L.wy) - 1);
+    const int32_t z0 = max(hz + dmin, 0), z1 = min(hz + dmin + W - 1, (1 << L.wz) - 1);
+    if (x0 > x1) return;
+    for (int32_t gz = max(z0, oz); gz <= z1; ++gz) {
+        double d = qz - nm_centre(gz, L.min_z, L.edge, L.half_edge);
+        const double dz2 = d * d;
+        for (int32_t gy = gz == oz ? max(y0, oy) : y0; gy <= y1; ++gy) {
+            d = qy - nm_centre(gy, L.min_y, L.edge, L.half_edge);
+            const double dy2 = d * d;
+            if (!(dy2 + dz2 <= r2)) continue;
+            const int32_t xs = (gz == oz && gy == oy) ? max(x0, ox + 1) : x0;      // the own row: above the own bit
+            if (xs > x1) continue;
+            const uint32_t wrow = (((uint32_t)gz & 7u) << 3) | ((uint32_t)gy & 7u);
+            for (int32_t sbx = xs >> NM_SBX_BITS; sbx <= (x1 >> NM_SBX_BITS); ++sbx) {
+                const uint64_t at = nm_sb_key((uint32_t)sbx, (uint32_t)gy >> NM_SBY_BITS,
+                                              (uint32_t)gz >> NM_SBZ_BITS, L) * NM_LEAF_WORDS + wrow;
+                const uint32_t all = leaf[at];
+                const int32_t base = sbx << NM_SBX_BITS;
+                const int32_t lo = max(xs - base, 0), hi = min(x1 - base, 31);
+                uint32_t word = all & (0xFFFFFFFFu >> (31 - hi)) & (0xFFFFFFFFu << lo);
+                if (!word) continue;
+                const uint32_t r0 = rank[at];
+                while (word) {
+                    const int bit = __ffs((int)word) - 1;
+                    word &= word - 1u;
+                    d = qx - nm_centre(base + bit, L.min_x, L.edge, L.half_edge);
+                    const double s = (d * d + dy2) + dz2;
+                    if (!(s <= r2)) continue;
+                    hit(r0 + (uint32_t)__popc(all & ((1u << bit) - 1u)));
+                }
+            }
+        }
+    }
+}
+
+// init: every voxel of the graph its own tree, the others CC_NONE (the pad of the scratch too); sizes and marks zero
+__global__ __launch_bounds__(256) void k_cc_init(const uint32_t* __restrict__ index_header, uint32_t room,
+                                                 const int64_t* __restrict__ cls, uint32_t* __restrict__ parent,
+                                                 uint32_t* __restrict__ keep, int64_t* __restrict__ size,
+                                                 int64_t* __restrict__ d_count)
+{
+    const uint32_t m = cc_voxels(index_header, room);
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;       // (room <= 2^31)
+    if (v >= room) return;
+    parent[v] = (v < m && !(cls && cls[v] < 0)) ? v : CC_NONE;
+    keep[v] = 0u;
+    size[v] = 0;
+    if (v == 0) d_count[1] = 0;
+}
+
+// link: one lane per voxel, every forward neighbor of its class joined to it
+__global__ __launch_bounds__(256) void k_cc_link(const int64_t* __restrict__ addr,
+                                                 const uint32_t* __restrict__ index_header, uint32_t room,
+                                                 const uint32_t* __restrict__ leaf,
+                                                 const uint32_t* __restrict__ rank, LatticeDev L, double r2,
+                                                 int32_t dmin, int32_t W, const int64_t* __restrict__ cls,
+                                                 uint32_t* parent)
+{
+    const uint32_t m = cc_voxels(index_header, room);
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= m) return;
+    const int64_t c = cls ? cls[v] : 0;
+    if (c < 0) return;
+    const int64_t a = addr[v];
+    const int32_t ox = (int32_t)(a & (((int64_t)1 << L.wx) - 1));
+    const int32_t oy = (int32_t)((a >> L.s0) & (((int64_t)1 << L.wy) - 1));
+    const int32_t oz = (int32_t)(a >> L.s1);
+    uint32_t mine = v;       // a node of v's tree, as near its root as this lane has seen
+    nbr_walk_forward(ox, oy, oz, leaf, rank, L, r2, dmin, W, [&](uint32_t u) {
+        if (cls && cls[u] != c) return;
+        mine = cc_join(parent, mine, u);
+    });
+}
+
+// flatten: parent[v] = the root, and the root's size += the voxel's weight.  a cloud that is one component would send
+// M adds to one word: a wave adds once per DISTINCT root among its lanes, and the first of them - in a large
+// component the only one - goes through LDS, where the block's waves that share it make one add of it
+constexpr int CC_FLAT_THREADS = 1024;
+__global__ __launch_bounds__(CC_FLAT_THREADS) void k_cc_flatten(const uint32_t* __restrict__ index_header,
+                                                                uint32_t room, const int64_t* __restrict__ weight,
+                                                                uint32_t* parent, int64_t* __restrict__ size)
+{
+    constexpr int WAVES = CC_FLAT_THREADS / 64;
+    __shared__ uint32_t first_root[WAVES];
+    __shared__ long long first_sum[WAVES];
+    const uint32_t m = cc_voxels(index_header, room);
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t root = CC_NONE;
+    long long w = 0;
+    if (v < m) {
+        const uint32_t p = cc_load(parent + v);
+        if (p != CC_NONE) {
+            root = cc_root(parent, p);
+            if (root != p) cc_store(parent + v, root);
+            w = weight ? (long long)weight[v] : 1;
+        }
+    }
+    // (no lane has left: the shuffles below see all 64)
+    if (lane == 0) first_root[wave] = CC_NONE;
+    unsigned long long pending = __ballot(root != CC_NONE);
+    bool first = true;
+    while (pending) {
+        const int leader = __ffsll((long long)pending) - 1;
+        const uint32_t r0 = __shfl(root, leader);
+        const bool same = root == r0;
+        long long s = same ? w : 0;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+        if (lane == leader) {
+            if (first) {
+                first_root[wave] = r0;
+                first_sum[wave] = s;
+            } else {
+                atomicAdd((unsigned long long*)&size[r0], (unsigned long long)s);
+            }
+        }
+        first = false;
+        pending &= ~__ballot(same);
+    }
+    __syncthreads();
+    if (threadIdx.x < WAVES) {
+        // thread t speaks for wave t's first root unless an earlier wave has the same one
+        const uint32_t r = first_root[threadIdx.x];
+        long long s = r != CC_NONE ? first_sum[threadIdx.x] : 0;
+        bool speaks = r != CC_NONE;
+        for (int j = 0; j < WAVES; ++j) {
+            const bool match = j != (int)threadIdx.x && first_root[j] == r;
+            if (match && j < (int)threadIdx.x) speaks = false;
+            if (match && j > (int)threadIdx.x && r != CC_NONE) s += first_sum[j];
+        }
+        if (speaks) atomicAdd((unsigned long long*)&size[r], (unsigned long long)s);
+    }
+}
+
+// number, before the scan: the roots of the components that stay; all roots are counted
+__global__ __launch_bounds__(256) void k_cc_mark(const uint32_t* __restrict__ index_header, uint32_t room,
+                                                 const uint32_t* __restrict__ parent,
+                                                 const int64_t* __restrict__ size, int64_t min_size,
+                                                 uint32_t* __restrict__ keep, int64_t* __restrict__ d_count)
+{
+    const uint32_t m = cc_voxels(index_header, room);
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool is_root = v < m && parent[v] == v;
+    if (is_root && size[v] >= min_size) keep[v] = 1u;
+    const unsigned long long roots = __ballot(is_root);
+    if (roots && (threadIdx.x & 63) == 0)
+        atomicAdd((unsigned long long*)(d_count + 1), (unsigned long long)__popcll(roots));
+}
+
+// number, behind the scan: id[] = keep[] scanned, so a kept root's entry is its component's number - roots in
+// ascending position, which is ascending smallest member
+__global__ __launch_bounds__(256) void k_cc_label(const uint32_t* __restrict__ index_header, uint32_t room,
+                                                  const uint32_t* __restrict__ parent,
+                                                  const int64_t* __restrict__ size, int64_t min_size,
+                                                  const uint32_t* __restrict__ id, int64_t* __restrict__ label,
+                                                  int64_t* __restrict__ sizes, int64_t* __restrict__ d_count)
+{
+    const uint32_t m = index_header[0];
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m > room) {          // the scratch was made for fewer voxels than the index holds: nothing was labelled
+        if (v == 0) d_count[0] = d_count[1] = -1;
+        return;
+    }
+    if (v >= m) return;
+    const uint32_t r = parent[v];
+    int64_t out = -1;
+    if (r != CC_NONE) {
+        const int64_t s = size[r];
+        if (s >= min_size) {
+            out = (int64_t)id[r];
+            if (r == v) sizes[out] = s;
+        }
+    }
+    label[v] = out;
+}
+
 // argument checks shared by the entry points that take a built workspace
 int nbr_check_index(nm_ctx* ctx, const char* who, const nm_lattice* lat, const void* d_work, size_t work_bytes,
                     LatticeDev* L, NbrPlan* P)
@@ -936,7 +1261,7 @@ extern "C" int nm_neighbor_index_addresses(nm_ctx* ctx, const nm_lattice* lat, c
     const uint64_t words = P.superblocks * NM_LEAF_WORDS;
     k_nbr_addresses<<<(unsigned)((words + 255) / 256), 256, 0, (hipStream_t)stream>>>(
         (const uint32_t*)(w + P.off_leaf), (const uint32_t*)(w + P.off_rank), (const uint32_t*)w, L, words,
-        d_addr_out);
+        d_addr_out, 0xFFFFFFFFu);
     NM_HIP(ctx, hipGetLastError());
     return NM_OK;
 }
@@ -1169,6 +1494,61 @@ extern "C" int nm_neighbor_index_nearest(nm_ctx* ctx, const double* d_query, int
     else if (k <= 16) NM_NEAREST_LAUNCH(16);
     else NM_NEAREST_LAUNCH(32);
 #undef NM_NEAREST_LAUNCH
+    NM_HIP(ctx, hipGetLastError());
+    return NM_OK;
+}
+
+// ---- connected components of the voxel graph (additive within ABI 7) ---------------------------------------------------
+
+extern "C" size_t nm_neighbor_index_components_workspace_bytes(int64_t n_voxels)
+{
+    if (n_voxels < 0 || n_voxels >= (int64_t)1 << 31) return 0;
+    return cc_plan(n_voxels).bytes;
+}
+
+extern "C" int nm_neighbor_index_components(nm_ctx* ctx, const nm_lattice* lat, double radius, const void* d_work,
+                                            size_t work_bytes, const int64_t* d_class, const int64_t* d_weight,
+                                            int64_t min_size, int64_t* d_label, int64_t* d_size, int64_t* d_count,
+                                            void* d_tmp, size_t tmp_bytes, void* stream)
+{
+    NM_ENTER_STREAM(ctx, stream);
+    if (!d_label || !d_size || !d_count) NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_components: bad arguments");
+    LatticeDev L;
+    NbrPlan P;
+    int rc = nbr_check_index(ctx, "nm_neighbor_index_components", lat, d_work, work_bytes, &L, &P);
+    if (rc) return rc;
+    int32_t dmin = 0;
+    const int W = radius >= 0.0 ? nbr_candidate_width(radius, lat->edge, &dmin) : -1;      // (NaN fails)
+    if (W < 0) NM_FAIL(ctx, NM_ERR_RADIUS, "radius/edge ratio outside the supported range");
+    if (!d_tmp || tmp_bytes < cc_plan(0).bytes)
+        NM_FAIL(ctx, NM_ERR_WORKSPACE, "nm_neighbor_index_components: temporary workspace too small");
+    const CcPlan C = cc_plan_of(tmp_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    const char* w = (const char*)d_work;
+    const uint32_t* index_header = (const uint32_t*)w;
+    const uint32_t* leaf = (const uint32_t*)(w + P.off_leaf);
+    const uint32_t* rank = (const uint32_t*)(w + P.off_rank);
+    char* t = (char*)d_tmp;
+    uint32_t* header = (uint32_t*)t;
+    uint32_t* partial = (uint32_t*)(t + C.off_partial);
+    int64_t* addr = (int64_t*)(t + C.off_addr);
+    int64_t* size = (int64_t*)(t + C.off_size);
+    uint32_t* parent = (uint32_t*)(t + C.off_parent);
+    uint32_t* keep = (uint32_t*)(t + C.off_keep);
+    const uint32_t room = (uint32_t)C.room;
+    const unsigned blocks = (unsigned)(C.room / 256);
+    const uint64_t words = P.superblocks * NM_LEAF_WORDS;
+    k_nbr_addresses<<<(unsigned)((words + 255) / 256), 256, 0, s>>>(leaf, rank, index_header, L, words, addr, room);
+    k_cc_init<<<blocks, 256, 0, s>>>(index_header, room, d_class, parent, keep, size, d_count);
+    k_cc_link<<<blocks, 256, 0, s>>>(addr, index_header, room, leaf, rank, L, radius * radius, dmin, W, d_class,
+                                     parent);
+    k_cc_flatten<<<(unsigned)(C.room / CC_FLAT_THREADS), CC_FLAT_THREADS, 0, s>>>(index_header, room, d_weight,
+                                                                                  parent, size);
+    k_cc_mark<<<blocks, 256, 0, s>>>(index_header, room, parent, size, min_size, keep, d_count);
+    k_nbr_scan_reduce<<<C.scan_blocks, NBR_SCAN_THREADS, 0, s>>>(keep, C.tiles_per_block, C.room, partial);
+    k_nbr_scan_apply<<<C.scan_blocks, NBR_SCAN_THREADS, 0, s>>>(keep, C.tiles_per_block, C.room, partial, header,
+                                                                d_count);
+    k_cc_label<<<blocks, 256, 0, s>>>(index_header, room, parent, size, min_size, keep, d_label, d_size, d_count);
     NM_HIP(ctx, hipGetLastError());
     return NM_OK;
 }

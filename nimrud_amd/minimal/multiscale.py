@@ -295,8 +295,10 @@ class NeighborIndex(object):
                                 over the voxels lists() would name, without writing the lists
         .nearest(query_cloud, k, max_distance=None) -> (distance (Nq, k), index (Nq, k)): the k nearest voxels
                                 of every query point (cKDTree(voxels()).query), ties by the smaller position
-    torch in, torch out; numpy in, numpy out (addresses / voxels / point_counts / members follow the search
-    cloud, lists / neighborhood_stats / nearest the query cloud, voxel_of and voxel_table their argument)."""
+        .components(radius, voxel_class=None, voxel_weight=None, min_size=1) -> (labels (M,), sizes (C,)): the
+                                connected components of the graph lists(voxels(), radius) spans, without the lists
+    torch in, torch out; numpy in, numpy out (addresses / voxels / point_counts / members / components follow the
+    search cloud, lists / neighborhood_stats / nearest the query cloud, voxel_of and voxel_table their argument)."""
 
     def __init__(self, search_cloud, edge_length, method="auto"):
         if method not in ("auto", "index", "search"):
@@ -566,6 +568,67 @@ class NeighborIndex(object):
             return distance, index
         return distance.cpu().numpy(), index.cpu().numpy()
 
+    def _voxel_integers(self, values, what):
+        """an integer array with one entry per voxel as an int64 device tensor (M,)"""
+        return _integer_column(values, self.n_voxels, self._rt.device, what, "voxel")
+
+    def _components_device(self, radius, voxel_class, voxel_weight, min_size):
+        """enqueue nm_neighbor_index_components on int64 device tensors (or None); one host read, of the counts"""
+        rt = self._rt
+        m = self.n_voxels
+        labels = torch.empty(m, dtype=torch.int64, device=rt.device)
+        sizes = torch.empty(max(m, 1), dtype=torch.int64, device=rt.device)
+        if m == 0:
+            return labels, sizes[:0]
+        count = torch.empty(2, dtype=torch.int64, device=rt.device)
+        nbytes = int(rt.lib.nm_neighbor_index_components_workspace_bytes(m))
+        tmp = rt.workspace(nbytes)
+        rt.check(rt.lib.nm_neighbor_index_components(
+            rt.ctx, ctypes.byref(self.filter.nm_lattice), radius, _device.ptr(self._work), self._work.numel(),
+            _device.ptr(voxel_class), _device.ptr(voxel_weight), min_size, _device.ptr(labels), _device.ptr(sizes),
+            _device.ptr(count), _device.ptr(tmp), nbytes, rt.stream()))
+        kept = int(count[0])
+        if kept < 0:        # (cannot happen: the scratch was sized for this handle's M)
+            raise _ffi.NimrudHipError("nm_neighbor_index_components: scratch too small for the index")
+        return labels, sizes[:kept]
+
+    def components(self, radius, voxel_class=None, voxel_weight=None, min_size=1):
+        """(labels int64 (M,), sizes int64 (C,)): the connected components of the voxel graph - Euclidean cluster
+        extraction.  voxels u and v are joined when lists(voxels(), radius) names one for the other (the limit is
+        inclusive), and a component is what can be reached in such steps.  no edge list is written.
+        voxel_class (integers, (M,)): a negative class takes the voxel out of the graph, and an edge joins voxels of
+        equal class only, so one call segments every class; None is one class for all.  voxel_weight (integers,
+        (M,), e.g. point_counts()): a component's size is the sum of its weights; None counts voxels.  components
+        of a size below min_size are dropped.  kept components are numbered 0..C-1 in ascending order of their
+        smallest voxel position; voxels outside the graph or in a dropped component get -1.  the result is a
+        function of the arguments alone, the same bit for bit on every run."""
+        self._need_index("components")
+        radius = float(radius)
+        if not radius >= 0.0:
+            raise ValueError("radius must be a number >= 0")
+        if isinstance(min_size, bool) or not isinstance(min_size, (int, np.integer)):
+            raise ValueError("min_size must be an integer")
+        cls = None if voxel_class is None else self._voxel_integers(voxel_class, "voxel_class")
+        weight = None if voxel_weight is None else self._voxel_integers(voxel_weight, "voxel_weight")
+        labels, sizes = self._components_device(radius, cls, weight, int(min_size))
+        return (labels, sizes) if self._as_torch else (labels.cpu().numpy(), sizes.cpu().numpy())
+
+
+def _integer_column(values, n, device, what, per):
+    """an integer array (n,) - torch or numpy, any integer width - as a contiguous int64 tensor on `device`"""
+    if isinstance(values, torch.Tensor):
+        integral = values.dtype in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+        t = values
+    else:
+        arr = np.asarray(values)
+        integral = arr.dtype.kind in "iu"
+        t = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.int64)) if integral else None
+    if not integral:
+        raise ValueError("%s must have an integer dtype" % what)
+    if t.ndim != 1 or t.shape[0] != n:
+        raise ValueError("%s must have one entry per %s" % (what, per))
+    return t.to(device=device, dtype=torch.int64).contiguous()
+
 
 def _unit_columns(table):
     """the table itself where its rows can be walked with a row stride, else a contiguous copy"""
@@ -593,3 +656,34 @@ def nearest_voxels(query_cloud, search_cloud, edge_length, k, max_distance=None)
     multiscale.py:87 - see NeighborIndex.nearest for order, ties, limit and padding.  one NeighborIndex (method
     "index"), built and asked once - keep the handle yourself to ask again."""
     return NeighborIndex(search_cloud, edge_length, method="index").nearest(query_cloud, k, max_distance)
+
+
+def cluster_cloud(cloud, edge_length, radius, point_class=None, min_points=1):
+    """(point_labels int64 (N,), sizes int64 (C,)): Euclidean cluster extraction of a cloud in one call.  the cloud
+    is voxel-filtered at `edge_length`, voxels whose centres lie within `radius` of each other are joined
+    (NeighborIndex.components), and every point takes the label of its voxel.  sizes and min_points count POINTS
+    (the voxels are weighted by point_counts()): clusters of fewer points are dropped, their points get -1.
+    clusters are numbered 0..C-1 in ascending order of their smallest voxel position.
+    point_class (integers, (N,), e.g. classify_cloud's labels; magnitudes below 2^53): only voxels of equal class
+    are joined.  a voxel's class is the MINIMUM class of the points in it, so a voxel with one point of a negative
+    class is out of the graph with all its points.
+    one NeighborIndex (method "index"), built and asked once.  torch in, torch out; numpy in, numpy out."""
+    index = NeighborIndex(cloud, edge_length, method="index")
+    rt = index._rt
+    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)):
+        raise ValueError("min_points must be an integer")
+    radius = float(radius)
+    if not radius >= 0.0:
+        raise ValueError("radius must be a number >= 0")
+    voxel_class = None
+    if point_class is not None:
+        column = _integer_column(point_class, index._search.shape[0], rt.device, "point_class", "point")
+        # min of an integer-valued fp64 column: exact
+        voxel_class = index.voxel_table(column.to(torch.float64), reduce="min")[:, 0].to(torch.int64)
+    weight = index._grouping()[0]
+    labels, sizes = index._components_device(radius, voxel_class, weight, int(min_points))
+    voxel = index._voxel_of_device(index._search)
+    point_labels = torch.where(voxel >= 0, labels[voxel.clamp(min=0)], torch.full_like(voxel, -1))
+    if isinstance(cloud, torch.Tensor):
+        return point_labels, sizes
+    return point_labels.cpu().numpy(), sizes.cpu().numpy()
