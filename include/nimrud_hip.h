@@ -379,6 +379,54 @@ int nm_neighbor_index_components(nm_ctx* ctx, const nm_lattice* lat, double radi
                                  int64_t min_size, int64_t* d_label, int64_t* d_size, int64_t* d_count,
                                  void* d_tmp, size_t tmp_bytes, void* stream);
 
+/* ---- per-segment descriptors of a labelled cloud (new symbols only: additive within ABI 7) --------------------
+ * what a cluster is as an object: how many points, where, its box, its shape and which way it points.  the last
+ * stage behind a classifier and nm_neighbor_index_components; the table is a plain fp64 feature matrix.
+ *   input: d_xyz rows of `stride` doubles (x, y, z first) - cloud points, or voxel centres with point counts as
+ *     weights; d_label[n]: a value in [0, n_segments) names the row's segment, anything else (-1, >= n_segments)
+ *     puts the row in no segment; d_weight[n] (may be NULL = 1 each): integers >= 0, frequency weights as
+ *     np.cov(..., fweights=).  a row of weight 0 counts for nothing: not for the box, not as a row.  negative weights
+ *     and NaN coordinates are unsupported and unchecked.  n, n_segments < 2^31, sum of weights < 2^53.
+ *   output: row s of d_table (table_stride >= NM_SEGMENT_COLUMNS doubles apart; columns from 25 on are not touched):
+ *       0       n = sum of weights (an integer sum, exact)
+ *       1-3     centroid
+ *       4-6     bounding box minimum xyz (exact)          7-9   maximum xyz (exact)
+ *       10-15   covariance [xx, xy, xz, yy, yz, zz], ddof = 1 (the layout of nm_set_covariance_output)
+ *       16-18   its eigenvalues, descending (the solver of the feature kernels, on the matrix scaled to unit trace)
+ *       19-21   unit eigenvector of the smallest eigenvalue (the normal); sign as nm_set_normal_output: the last
+ *               non-zero of x, y, z positive
+ *       22-24   unit eigenvector of the largest eigenvalue (the axis), same construction and sign rule
+ *   degenerate segments: no rows, or n == 0: all zeros.  n < 2: covariance, eigenvalues and both vectors zeros.
+ *     fewer than 3 rows, or a zero trace: both vectors zeros.  an eigenvalue that is not simple: its vector is some
+ *     unit vector of the eigenspace.
+ *   arithmetic: n, the row count and the box first (integer sums, minima and maxima: exact in any order).  the pivot
+ *     of a segment is its box minimum; d = p - pivot in fp64, S1 = sum of w d, S2 = sum of w d (x) d, then
+ *     centroid = pivot + S1 / n and cov = (S2 - S1 S1^T / n) / (n - 1).  no raw moments of p (they lose every digit
+ *     on georeferenced coordinates), no floating-point atomics, nothing fused.
+ *   order: the summation tree of a segment is a function of its ASCENDING row list alone - not of n, of the other
+ *     segments, of where its rows lie in the cloud, of the launch or of the run; results repeat bit for bit.
+ *       - the list is cut into consecutive chunks of NM_SEGMENT_CHUNK = 256 rows, counted from the segment's start;
+ *       - chunk tree: slot j of 64 adds the terms of rows j, j + 64, j + 128, j + 192 of the chunk left to right;
+ *         the slots are then added pairwise, neighbours first: j += j + 1 (j even), j += j + 2 (j % 4 == 0), ...,
+ *         j += j + 32.  an absent row is +0;
+ *       - segment tree: slot j of 64 adds the chunk sums j, j + 64, j + 128, ... left to right, then the same
+ *         pairwise steps.
+ *     the term of a row for S1 is w * d, for S2 (w * d_a) * d_b.
+ *   work is dealt out by chunks, not by segments: one segment holding every row occupies the device, and segments of
+ *     up to 8 rows take eight lanes each.
+ *   d_tmp: nm_segment_table_workspace_bytes(n, n_segments) bytes; the query needs no GPU, is monotone in both
+ *     arguments and 0 for negative sizes or sizes >= 2^31.
+ *   n == 0 with n_segments > 0 zero-fills the table; n_segments == 0 is NM_OK and does nothing.
+ *   errors, all before anything is queued: NM_ERR_INVALID for null pointers, negative sizes, sizes >= 2^31,
+ *     stride < 3, table_stride < NM_SEGMENT_COLUMNS; NM_ERR_WORKSPACE for too small a d_tmp.  nothing here waits for
+ *     the device.                                                                                                */
+#define NM_SEGMENT_COLUMNS 25
+#define NM_SEGMENT_CHUNK 256
+size_t nm_segment_table_workspace_bytes(int64_t n, int64_t n_segments);
+int nm_segment_table(nm_ctx* ctx, const double* d_xyz, int64_t n, int64_t stride, const int64_t* d_label,
+                     int64_t n_segments, const int64_t* d_weight, double* d_table, int64_t table_stride,
+                     void* d_tmp, size_t tmp_bytes, void* stream);
+
 /* ---- explicit neighborhoods -----------------------------------------------------------------------
  * features.population / centroid / pca (features.py:21-57) for a batch of explicit neighborhoods
  * given as CSR over a point array: neighborhood b is d_points[d_offsets[b] .. d_offsets[b+1]) (rows

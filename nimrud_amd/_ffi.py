@@ -24,6 +24,8 @@ NM_COMM_ID_BYTES = 128
 ABI_VERSION = 7
 NM_STATS_MAX_DIMS = 16
 NM_NEAREST_MAX_K = 32
+NM_SEGMENT_COLUMNS = 25
+NM_SEGMENT_CHUNK = 256
 NM_REDUCE = {"mean": 0, "sum": 1, "min": 2, "max": 3}      # NM_REDUCE_MEAN .. NM_REDUCE_MAX
 
 c_i64 = ctypes.c_int64
@@ -124,6 +126,9 @@ SIGNATURES = {
     "nm_neighbor_index_components": (ctypes.c_int,
                                      [c_ptr, _LATP, c_f64, c_ptr, c_size, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr,
                                       c_ptr, c_size, c_ptr]),
+    "nm_segment_table_workspace_bytes": (c_size, [c_i64, c_i64]),
+    "nm_segment_table": (ctypes.c_int,
+                         [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_size, c_ptr]),
     "nm_neighborhood_features": (ctypes.c_int,
                                  [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
     "nm_halo_count": (ctypes.c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_i32, c_i32, c_ptr, c_ptr]),

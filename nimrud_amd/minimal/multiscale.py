@@ -297,6 +297,8 @@ class NeighborIndex(object):
                                 of every query point (cKDTree(voxels()).query), ties by the smaller position
         .components(radius, voxel_class=None, voxel_weight=None, min_size=1) -> (labels (M,), sizes (C,)): the
                                 connected components of the graph lists(voxels(), radius) spans, without the lists
+        .component_table(labels, voxel_weight=None) -> (C, 25): one row of descriptors per component (segment_table
+                                over voxels())
     torch in, torch out; numpy in, numpy out (addresses / voxels / point_counts / members / components follow the
     search cloud, lists / neighborhood_stats / nearest the query cloud, voxel_of and voxel_table their argument)."""
 
@@ -613,6 +615,20 @@ class NeighborIndex(object):
         labels, sizes = self._components_device(radius, cls, weight, int(min_size))
         return (labels, sizes) if self._as_torch else (labels.cpu().numpy(), sizes.cpu().numpy())
 
+    def component_table(self, labels, voxel_weight=None):
+        """fp64 (C, 25): segment_table over voxels() for the labels components() returned - one row of descriptors
+        per component of the voxel graph (columns: SEGMENT_COLUMNS).  voxels with label -1 are in no segment.
+        voxel_weight (integers, (M,), e.g. point_counts()): frequency weights, so that column 0 is the component's
+        size in points; None counts voxels.  C is labels.max() + 1 (one host read).  follows the search cloud:
+        torch in, torch out; numpy in, numpy out."""
+        self._need_index("component_table")
+        rt = self._rt
+        label = self._voxel_integers(labels, "labels")
+        weight = None if voxel_weight is None else self._voxel_integers(voxel_weight, "voxel_weight")
+        centres = self.filter.address_to_coordinate(self._addresses_device())
+        table = _segment_table_device(rt, centres, label, weight, None)
+        return table if self._as_torch else table.cpu().numpy()
+
 
 def _integer_column(values, n, device, what, per):
     """an integer array (n,) - torch or numpy, any integer width - as a contiguous int64 tensor on `device`"""
@@ -687,3 +703,72 @@ def cluster_cloud(cloud, edge_length, radius, point_class=None, min_points=1):
     if isinstance(cloud, torch.Tensor):
         return point_labels, sizes
     return point_labels.cpu().numpy(), sizes.cpu().numpy()
+
+
+# columns of a segment table (nm_segment_table): name -> slice
+SEGMENT_COLUMNS = {
+    "n": slice(0, 1),
+    "centroid": slice(1, 4),
+    "min": slice(4, 7),
+    "max": slice(7, 10),
+    "covariance": slice(10, 16),        # [xx, xy, xz, yy, yz, zz], ddof = 1
+    "eigenvalues": slice(16, 19),       # descending
+    "normal": slice(19, 22),            # unit eigenvector of the smallest eigenvalue
+    "axis": slice(22, 25),              # unit eigenvector of the largest eigenvalue
+}
+
+
+def _segment_table_device(rt, points, label, weight, n_segments):
+    """enqueue nm_segment_table on device tensors: points fp64 (N, >= 3), label int64 (N,), weight int64 (N,) or
+    None -> fp64 (C, 25).  n_segments None: label.max() + 1, one host read (0 without rows or labels)."""
+    n = int(points.shape[0])
+    if n_segments is None:
+        n_segments = int(label.max()) + 1 if n else 0
+        n_segments = max(n_segments, 0)
+    elif isinstance(n_segments, bool) or not isinstance(n_segments, (int, np.integer)) or n_segments < 0:
+        raise ValueError("n_segments must be an integer >= 0")
+    c = int(n_segments)
+    table = torch.empty((c, _ffi.NM_SEGMENT_COLUMNS), dtype=torch.float64, device=rt.device)
+    if c == 0:
+        return table
+    nbytes = int(rt.lib.nm_segment_table_workspace_bytes(n, c))
+    if nbytes == 0:
+        raise ValueError("segment_table: sizes must be below 2^31")
+    tmp = rt.workspace(nbytes)
+    rt.check(rt.lib.nm_segment_table(
+        rt.ctx, _device.ptr(points), n, _device.row_stride(points), _device.ptr(label), c, _device.ptr(weight),
+        _device.ptr(table), _ffi.NM_SEGMENT_COLUMNS, _device.ptr(tmp), tmp.numel(), rt.stream()))
+    return table
+
+
+def segment_table(cloud, labels, weights=None, n_segments=None):
+    """fp64 (C, 25): one row of descriptors per segment of a labelled cloud (nm_segment_table; columns:
+    SEGMENT_COLUMNS) - n, centroid, bounding box, ddof=1 covariance, its eigenvalues (descending), the normal (unit
+    eigenvector of the smallest) and the axis (of the largest), both with their last non-zero component positive.
+    labels (integers, (N,)): a value in [0, C) names the point's segment; -1 or anything else is no segment.
+    weights (integers >= 0, (N,)): frequency weights as np.cov(fweights=), e.g. point counts of voxel centres; a row of
+    weight 0 counts for nothing.  n_segments: C; None takes labels.max() + 1 (one host read).
+    empty segments are zeros; with n < 2 the covariance and all behind it, with fewer than 3 rows the vectors.  the
+    moments are taken about the segment's box minimum, so georeferenced coordinates keep their digits; the summation
+    order is a function of the segment's own ascending rows, the same bit for bit on every run, whatever else the
+    cloud holds.  a ForestModel takes the table as it is.  torch in, torch out; numpy in, numpy out."""
+    rt, points = _device.as_cloud(cloud)
+    if points.shape[1] < 3:
+        raise ValueError("only 3D spaces supported by the multiscale pipeline")
+    n = int(points.shape[0])
+    label = _integer_column(labels, n, rt.device, "labels", "point")
+    weight = None if weights is None else _integer_column(weights, n, rt.device, "weights", "point")
+    table = _segment_table_device(rt, points, label, weight, n_segments)
+    return table if isinstance(cloud, torch.Tensor) else table.cpu().numpy()
+
+
+def cluster_features(cloud, edge_length, radius, point_class=None, min_points=1):
+    """(point_labels int64 (N,), sizes int64 (C,), table fp64 (C, 25)): cluster_cloud followed by segment_table over
+    the points - every cluster with its descriptors, table[:, 0] == sizes.  arguments as cluster_cloud; the cloud is
+    uploaded once.  torch in, torch out; numpy in, numpy out."""
+    rt, points = _device.as_cloud(cloud)
+    point_labels, sizes = cluster_cloud(points, edge_length, radius, point_class=point_class, min_points=min_points)
+    table = _segment_table_device(rt, points, point_labels, None, int(sizes.shape[0]))
+    if isinstance(cloud, torch.Tensor):
+        return point_labels, sizes, table
+    return point_labels.cpu().numpy(), sizes.cpu().numpy(), table.cpu().numpy()
