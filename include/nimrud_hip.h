@@ -379,6 +379,37 @@ int nm_neighbor_index_components(nm_ctx* ctx, const nm_lattice* lat, double radi
                                  int64_t min_size, int64_t* d_label, int64_t* d_size, int64_t* d_count,
                                  void* d_tmp, size_t tmp_bytes, void* stream);
 
+/* ---- density-based clusters (DBSCAN) of the voxel graph (new symbols only: additive within ABI 7) -------------
+ * the graph of nm_neighbor_index_components, but a voxel links only where the cloud is dense, so one chain of
+ * stray voxels no longer welds two objects into one.  no list is written and nothing is sorted.
+ *   graph: as nm_neighbor_index_components - u ~ v iff the lists name one for the other and both carry the same
+ *     class >= 0; a voxel of negative class is out of the graph: label -1, core 0, density 0.
+ *   density[v] = the sum of d_weight over v itself and its neighbors (an int64 sum; d_weight NULL = 1 each, so the
+ *     density counts voxels).  weights are integers >= 0; negative weights are unsupported and unchecked.
+ *   core[v] = density[v] >= min_weight (sklearn's min_samples with sample_weight, the point itself included).
+ *   clusters: the connected components of the graph restricted to core voxels.
+ *   border: a voxel of the graph that is not core and has a core neighbor joins the cluster of its NEAREST core
+ *     neighbor, ordered by (d2 as the lists' test forms it, voxel position): equal distances go to the smaller
+ *     position.  a voxel of the graph that is not core and has no core neighbor is noise: label -1.
+ *   a cluster's size is the sum of the weights of all its members, core and border; clusters below min_size are
+ *     dropped and their members get -1 (d_core is not changed by that).  kept clusters are numbered 0..C-1 in
+ *     ascending order of their smallest CORE voxel position.  with d_weight NULL and min_weight <= 1 every voxel of
+ *     the graph is core, and labels, sizes and counts are those of nm_neighbor_index_components.
+ *   output: d_label[M], d_size (room for M entries), d_core[M] (0 / 1), d_density[M] (may be NULL: not wanted),
+ *     d_count (int64[3]) = {C = clusters kept, clusters before min_size, core voxels}.  all of it is a function of
+ *     the arguments alone, the same bit for bit on every run.
+ *   d_tmp: nm_neighbor_index_dbscan_workspace_bytes(M) bytes (16-byte aligned): the components scratch and 8 bytes
+ *     per voxel more; the query needs no GPU, is monotone in M and 0 for M < 0 or M >= 2^31.  a d_tmp that takes
+ *     the minimum (the query at 0) but not this index's M labels nothing and sets d_count to {-1, -1, -1}.
+ *   errors, all before anything is queued: NM_ERR_INVALID for a null output or lattice and for a NaN or negative
+ *     radius, NM_ERR_RADIUS as nm_neighbor_index_lists, NM_ERR_WORKSPACE for too small a d_work or a d_tmp below
+ *     the minimum, NM_ERR_LATTICE as every entry point that takes the index.  nothing here waits for the device. */
+size_t nm_neighbor_index_dbscan_workspace_bytes(int64_t n_voxels);
+int nm_neighbor_index_dbscan(nm_ctx* ctx, const nm_lattice* lat, double radius, int64_t min_weight,
+                             const void* d_work, size_t work_bytes, const int64_t* d_class, const int64_t* d_weight,
+                             int64_t min_size, int64_t* d_label, int64_t* d_size, uint8_t* d_core,
+                             int64_t* d_density, int64_t* d_count, void* d_tmp, size_t tmp_bytes, void* stream);
+
 /* ---- per-segment descriptors of a labelled cloud (new symbols only: additive within ABI 7) --------------------
  * what a cluster is as an object: how many points, where, its box, its shape and which way it points.  the last
  * stage behind a classifier and nm_neighbor_index_components; the table is a plain fp64 feature matrix.

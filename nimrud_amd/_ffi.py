@@ -126,6 +126,10 @@ SIGNATURES = {
     "nm_neighbor_index_components": (ctypes.c_int,
                                      [c_ptr, _LATP, c_f64, c_ptr, c_size, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr,
                                       c_ptr, c_size, c_ptr]),
+    "nm_neighbor_index_dbscan_workspace_bytes": (c_size, [c_i64]),
+    "nm_neighbor_index_dbscan": (ctypes.c_int,
+                                 [c_ptr, _LATP, c_f64, c_i64, c_ptr, c_size, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr,
+                                  c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "nm_segment_table_workspace_bytes": (c_size, [c_i64, c_i64]),
     "nm_segment_table": (ctypes.c_int,
                          [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_size, c_ptr]),

@@ -7,7 +7,8 @@
 // for any number of query clouds and radii: no sort, no address array, no search.
 // on the same index, attributes: the voxel of a point (np.unique's inverse), the rows of every voxel, per-voxel
 // reductions of per-point columns, and per-neighborhood count / mean / min / max of a voxel table without a list.
-// and the graph itself: the connected components of the voxels under "within r", by a lock-free union-find.
+// and the graph itself: the connected components of the voxels under "within r", by a lock-free union-find, and its
+// density-based clusters (DBSCAN): a density walk, the same union-find on the core voxels, a border walk.
 //
 // workspace (nm_neighbor_index_workspace_bytes), S = superblocks of the lattice (at most 2^NM_DENSE_LOG2):
 //   header  256 B      [0] M, written by the scan
@@ -295,11 +296,12 @@ __global__ __launch_bounds__(256) void k_nbr_addresses(const uint32_t* __restric
 // ---- the window walk: one lane per query ---------------------------------------------------------------------------
 // z outer, y inner, x inside the word: ascending address = ascending rank, so hit(voxel) is called in ascending
 // voxel order.  shared by the lists and the neighborhood statistics: same clamped home cell, same clipping, same
-// row skip, same unfused test
+// row skip, same unfused test.  nbr_walk_d2 hands hit(voxel, d2) the squared distance it tested as well; nbr_walk is
+// the same walk for a callback that has no use for it
 template <typename F>
-__device__ __forceinline__ void nbr_walk(double qx, double qy, double qz, const uint32_t* __restrict__ leaf,
-                                         const uint32_t* __restrict__ rank, const LatticeDev& L, double r2,
-                                         int32_t dmin, int32_t W, F&& hit)
+__device__ __forceinline__ void nbr_walk_d2(double qx, double qy, double qz, const uint32_t* __restrict__ leaf,
+                                            const uint32_t* __restrict__ rank, const LatticeDev& L, double r2,
+                                            int32_t dmin, int32_t W, F&& hit)
 {
     const int32_t hx = nm_clamp_cell(nm_cell_f(qx, L.min_x, L.edge));
     const int32_t hy = nm_clamp_cell(nm_cell_f(qy, L.min_y, L.edge));
@@ -335,11 +337,19 @@ __device__ __forceinline__ void nbr_walk(double qx, double qy, double qz, const 
                     d = qx - nm_centre(base + bit, L.min_x, L.edge, L.half_edge);
                     const double s = (d * d + dy2) + dz2;
                     if (!(s <= r2)) continue;
-                    hit(r0 + (uint32_t)__popc(all & ((1u << bit) - 1u)));
+                    hit(r0 + (uint32_t)__popc(all & ((1u << bit) - 1u)), s);
                 }
             }
         }
     }
+}
+
+template <typename F>
+__device__ __forceinline__ void nbr_walk(double qx, double qy, double qz, const uint32_t* __restrict__ leaf,
+                                         const uint32_t* __restrict__ rank, const LatticeDev& L, double r2,
+                                         int32_t dmin, int32_t W, F&& hit)
+{
+    nbr_walk_d2(qx, qy, qz, leaf, rank, L, r2, dmin, W, [&](uint32_t voxel, double) { hit(voxel); });
 }
 
 // ---- lists: the voxels the walk finds, counted or written at the query's offset ---------------------------------
@@ -1187,6 +1197,130 @@ __global__ __launch_bounds__(256) void k_cc_label(const uint32_t* __restrict__ i
     label[v] = out;
 }
 
+// ---- dbscan: density-based clusters of the same graph -----------------------------------------------------------------
+// density[v] = the sum of the weights of v and of its neighbors of v's class (the FULL window: every voxel sees all
+// of its edges, nothing is shared between lanes); core[v] = density[v] >= min_weight.  the clusters are the components
+// of the graph restricted to core voxels: k_cc_init and k_cc_link as they are, on the EFFECTIVE class array eff[] =
+// the class of a core voxel and -1 for every other.  a voxel of the graph that is not core joins the cluster of its
+// nearest core neighbor by (d2, position) - border - or stays CC_NONE - noise; flatten, mark, scan and label then do
+// what they do for components: a border voxel adds its weight to its root, every root is a core voxel, and roots in
+// ascending position are clusters in ascending smallest CORE member.
+//
+// tmp (nm_neighbor_index_dbscan_workspace_bytes): the components layout for `room` voxels, then
+//   eff     room * 8   the effective class of every voxel
+struct DbPlan {
+    CcPlan C;
+    size_t off_eff, bytes;
+};
+
+DbPlan db_plan_tiles(int64_t tiles)
+{
+    DbPlan D;
+    D.C = cc_plan_tiles(tiles);
+    D.off_eff = D.C.bytes;
+    D.bytes = D.off_eff + (size_t)D.C.room * 8;
+    return D;
+}
+
+DbPlan db_plan(int64_t n) { return db_plan_tiles(n > 0 ? (n + NBR_SCAN_TILE - 1) / NBR_SCAN_TILE : 1); }
+
+// the plan a scratch of `bytes` has room for (at least db_plan(0).bytes), as cc_plan_of
+DbPlan db_plan_of(size_t bytes)
+{
+    const size_t fixed = db_plan(0).bytes - (size_t)NBR_SCAN_TILE * 32;
+    int64_t tiles = (int64_t)((bytes - fixed) / ((size_t)NBR_SCAN_TILE * 32));
+    const int64_t most = ((int64_t)1 << 31) / NBR_SCAN_TILE;
+    return db_plan_tiles(tiles < most ? tiles : most);
+}
+
+// the cell of voxel v from its address (as k_cc_link)
+__device__ __forceinline__ void db_cell(int64_t a, const LatticeDev& L, int32_t* ox, int32_t* oy, int32_t* oz)
+{
+    *ox = (int32_t)(a & (((int64_t)1 << L.wx) - 1));
+    *oy = (int32_t)((a >> L.s0) & (((int64_t)1 << L.wy) - 1));
+    *oz = (int32_t)(a >> L.s1);
+}
+
+// density: one lane per voxel, the lists' walk from the voxel's own centre (which finds the voxel itself, at d2 = 0),
+// an int64 sum in registers.  no atomics: every word written here is the lane's own
+__global__ __launch_bounds__(256) void k_db_density(const int64_t* __restrict__ addr,
+                                                    const uint32_t* __restrict__ index_header, uint32_t room,
+                                                    const uint32_t* __restrict__ leaf,
+                                                    const uint32_t* __restrict__ rank, LatticeDev L, double r2,
+                                                    int32_t dmin, int32_t W, const int64_t* __restrict__ cls,
+                                                    const int64_t* __restrict__ weight, int64_t min_weight,
+                                                    int64_t* __restrict__ density, uint8_t* __restrict__ core,
+                                                    int64_t* __restrict__ eff, int64_t* __restrict__ d_count)
+{
+    const uint32_t m = cc_voxels(index_header, room);
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v == 0) d_count[2] = 0;          // (the core voxels are counted by k_db_border)
+    if (v >= m) return;
+    const int64_t c = cls ? cls[v] : 0;
+    int64_t sum = 0;
+    if (c >= 0) {
+        int32_t ox, oy, oz;
+        db_cell(addr[v], L, &ox, &oy, &oz);
+        nbr_walk(nm_centre(ox, L.min_x, L.edge, L.half_edge), nm_centre(oy, L.min_y, L.edge, L.half_edge),
+                 nm_centre(oz, L.min_z, L.edge, L.half_edge), leaf, rank, L, r2, dmin, W, [&](uint32_t u) {
+                     if (cls && cls[u] != c) return;
+                     sum += weight ? weight[u] : 1;
+                 });
+    }
+    const bool is_core = c >= 0 && sum >= min_weight;
+    if (density) density[v] = sum;
+    core[v] = is_core ? 1 : 0;
+    eff[v] = is_core ? c : -1;
+}
+
+// border: runs when k_cc_link has finished.  a voxel of the graph that is not core walks its window again and keeps
+// the smallest (d2, position) among the core voxels of its class; the walk is in ascending position, so "strictly
+// smaller replaces" breaks equal distances towards the smaller position.  it then hangs itself under the ROOT of that
+// voxel's tree.  race-free without an atomic read-modify-write: only the lane of voxel v stores parent[v], and only
+// where v is not core; the words cc_root reads are those of core voxels (a tree of the link kernel holds core voxels
+// only, and no lane here walks up from a border voxel), which nobody writes in this kernel.  so every read sees the
+// finished forest and the result is a function of the arguments.  also counts the core voxels, once per wave
+__global__ __launch_bounds__(256) void k_db_border(const int64_t* __restrict__ addr,
+                                                   const uint32_t* __restrict__ index_header, uint32_t room,
+                                                   const uint32_t* __restrict__ leaf,
+                                                   const uint32_t* __restrict__ rank, LatticeDev L, double r2,
+                                                   int32_t dmin, int32_t W, const int64_t* __restrict__ cls,
+                                                   const int64_t* __restrict__ eff, uint32_t* parent,
+                                                   int64_t* __restrict__ d_count)
+{
+    const uint32_t m = index_header[0];
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m > room) {          // (as k_cc_label: the scratch was made for fewer voxels than the index holds)
+        if (v == 0) d_count[2] = -1;
+        return;
+    }
+    bool is_core = false;
+    if (v < m) {
+        is_core = eff[v] >= 0;
+        const int64_t c = cls ? cls[v] : 0;
+        if (!is_core && c >= 0) {
+            int32_t ox, oy, oz;
+            db_cell(addr[v], L, &ox, &oy, &oz);
+            double best_d2 = INFINITY;
+            uint32_t best = CC_NONE;
+            nbr_walk_d2(nm_centre(ox, L.min_x, L.edge, L.half_edge), nm_centre(oy, L.min_y, L.edge, L.half_edge),
+                        nm_centre(oz, L.min_z, L.edge, L.half_edge), leaf, rank, L, r2, dmin, W,
+                        [&](uint32_t u, double d2) {
+                            if (eff[u] != c) return;         // core, and of this voxel's class
+                            if (d2 < best_d2) {
+                                best_d2 = d2;
+                                best = u;
+                            }
+                        });
+            if (best != CC_NONE) cc_store(parent + v, cc_root(parent, best));
+        }
+    }
+    // (no lane has left)
+    const unsigned long long cores = __ballot(is_core);
+    if (cores && (threadIdx.x & 63) == 0)
+        atomicAdd((unsigned long long*)(d_count + 2), (unsigned long long)__popcll(cores));
+}
+
 // argument checks shared by the entry points that take a built workspace
 int nbr_check_index(nm_ctx* ctx, const char* who, const nm_lattice* lat, const void* d_work, size_t work_bytes,
                     LatticeDev* L, NbrPlan* P)
@@ -1542,6 +1676,72 @@ extern "C" int nm_neighbor_index_components(nm_ctx* ctx, const nm_lattice* lat, 
     k_cc_init<<<blocks, 256, 0, s>>>(index_header, room, d_class, parent, keep, size, d_count);
     k_cc_link<<<blocks, 256, 0, s>>>(addr, index_header, room, leaf, rank, L, radius * radius, dmin, W, d_class,
                                      parent);
+    k_cc_flatten<<<(unsigned)(C.room / CC_FLAT_THREADS), CC_FLAT_THREADS, 0, s>>>(index_header, room, d_weight,
+                                                                                  parent, size);
+    k_cc_mark<<<blocks, 256, 0, s>>>(index_header, room, parent, size, min_size, keep, d_count);
+    k_nbr_scan_reduce<<<C.scan_blocks, NBR_SCAN_THREADS, 0, s>>>(keep, C.tiles_per_block, C.room, partial);
+    k_nbr_scan_apply<<<C.scan_blocks, NBR_SCAN_THREADS, 0, s>>>(keep, C.tiles_per_block, C.room, partial, header,
+                                                                d_count);
+    k_cc_label<<<blocks, 256, 0, s>>>(index_header, room, parent, size, min_size, keep, d_label, d_size, d_count);
+    NM_HIP(ctx, hipGetLastError());
+    return NM_OK;
+}
+
+// ---- density-based clusters of the voxel graph (additive within ABI 7) -------------------------------------------------
+
+extern "C" size_t nm_neighbor_index_dbscan_workspace_bytes(int64_t n_voxels)
+{
+    if (n_voxels < 0 || n_voxels >= (int64_t)1 << 31) return 0;
+    return db_plan(n_voxels).bytes;
+}
+
+extern "C" int nm_neighbor_index_dbscan(nm_ctx* ctx, const nm_lattice* lat, double radius, int64_t min_weight,
+                                        const void* d_work, size_t work_bytes, const int64_t* d_class,
+                                        const int64_t* d_weight, int64_t min_size, int64_t* d_label,
+                                        int64_t* d_size, uint8_t* d_core, int64_t* d_density, int64_t* d_count,
+                                        void* d_tmp, size_t tmp_bytes, void* stream)
+{
+    NM_ENTER_STREAM(ctx, stream);
+    if (!d_label || !d_size || !d_core || !d_count)
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_dbscan: bad arguments");
+    if (!(radius >= 0.0))      // (NaN fails)
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_dbscan: radius must be >= 0");
+    LatticeDev L;
+    NbrPlan P;
+    int rc = nbr_check_index(ctx, "nm_neighbor_index_dbscan", lat, d_work, work_bytes, &L, &P);
+    if (rc) return rc;
+    int32_t dmin = 0;
+    const int W = nbr_candidate_width(radius, lat->edge, &dmin);
+    if (W < 0) NM_FAIL(ctx, NM_ERR_RADIUS, "radius/edge ratio outside the supported range");
+    if (!d_tmp || tmp_bytes < db_plan(0).bytes)
+        NM_FAIL(ctx, NM_ERR_WORKSPACE, "nm_neighbor_index_dbscan: temporary workspace too small");
+    const DbPlan D = db_plan_of(tmp_bytes);
+    const CcPlan& C = D.C;
+    hipStream_t s = (hipStream_t)stream;
+    const char* w = (const char*)d_work;
+    const uint32_t* index_header = (const uint32_t*)w;
+    const uint32_t* leaf = (const uint32_t*)(w + P.off_leaf);
+    const uint32_t* rank = (const uint32_t*)(w + P.off_rank);
+    char* t = (char*)d_tmp;
+    uint32_t* header = (uint32_t*)t;
+    uint32_t* partial = (uint32_t*)(t + C.off_partial);
+    int64_t* addr = (int64_t*)(t + C.off_addr);
+    int64_t* size = (int64_t*)(t + C.off_size);
+    uint32_t* parent = (uint32_t*)(t + C.off_parent);
+    uint32_t* keep = (uint32_t*)(t + C.off_keep);
+    int64_t* eff = (int64_t*)(t + D.off_eff);
+    const uint32_t room = (uint32_t)C.room;
+    const unsigned blocks = (unsigned)(C.room / 256);
+    const uint64_t words = P.superblocks * NM_LEAF_WORDS;
+    const double r2 = radius * radius;
+    k_nbr_addresses<<<(unsigned)((words + 255) / 256), 256, 0, s>>>(leaf, rank, index_header, L, words, addr, room);
+    k_db_density<<<blocks, 256, 0, s>>>(addr, index_header, room, leaf, rank, L, r2, dmin, W, d_class, d_weight,
+                                        min_weight, d_density, d_core, eff, d_count);
+    // the core clusters: components on the effective classes
+    k_cc_init<<<blocks, 256, 0, s>>>(index_header, room, eff, parent, keep, size, d_count);
+    k_cc_link<<<blocks, 256, 0, s>>>(addr, index_header, room, leaf, rank, L, r2, dmin, W, eff, parent);
+    k_db_border<<<blocks, 256, 0, s>>>(addr, index_header, room, leaf, rank, L, r2, dmin, W, d_class, eff, parent,
+                                       d_count);
     k_cc_flatten<<<(unsigned)(C.room / CC_FLAT_THREADS), CC_FLAT_THREADS, 0, s>>>(index_header, room, d_weight,
                                                                                   parent, size);
     k_cc_mark<<<blocks, 256, 0, s>>>(index_header, room, parent, size, min_size, keep, d_count);

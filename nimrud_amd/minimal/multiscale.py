@@ -297,9 +297,11 @@ class NeighborIndex(object):
                                 of every query point (cKDTree(voxels()).query), ties by the smaller position
         .components(radius, voxel_class=None, voxel_weight=None, min_size=1) -> (labels (M,), sizes (C,)): the
                                 connected components of the graph lists(voxels(), radius) spans, without the lists
+        .dbscan(radius, min_weight, voxel_weight=None, ...) -> (labels (M,), sizes (C,), core (M,)): components of the
+                                dense (core) voxels only, border voxels attached, the rest noise (-1)
         .component_table(labels, voxel_weight=None) -> (C, 25): one row of descriptors per component (segment_table
                                 over voxels())
-    torch in, torch out; numpy in, numpy out (addresses / voxels / point_counts / members / components follow the
+    torch in, torch out; numpy in, numpy out (addresses / voxels / point_counts / members / components / dbscan follow the
     search cloud, lists / neighborhood_stats / nearest the query cloud, voxel_of and voxel_table their argument)."""
 
     def __init__(self, search_cloud, edge_length, method="auto"):
@@ -615,6 +617,64 @@ class NeighborIndex(object):
         labels, sizes = self._components_device(radius, cls, weight, int(min_size))
         return (labels, sizes) if self._as_torch else (labels.cpu().numpy(), sizes.cpu().numpy())
 
+    def _dbscan_device(self, radius, min_weight, voxel_class, voxel_weight, min_size, want_density,
+                       check_weight=False):
+        """enqueue nm_neighbor_index_dbscan on int64 device tensors (or None): (labels, sizes, core bool, density or
+        None); one host read, of the counts - with check_weight the sign of the smallest weight comes down with them"""
+        rt = self._rt
+        m = self.n_voxels
+        labels = torch.empty(m, dtype=torch.int64, device=rt.device)
+        sizes = torch.empty(max(m, 1), dtype=torch.int64, device=rt.device)
+        core = torch.empty(m, dtype=torch.uint8, device=rt.device)
+        density = torch.empty(m, dtype=torch.int64, device=rt.device) if want_density else None
+        if m == 0:
+            return labels, sizes[:0], core.to(torch.bool), density
+        count = torch.empty(3, dtype=torch.int64, device=rt.device)
+        nbytes = int(rt.lib.nm_neighbor_index_dbscan_workspace_bytes(m))
+        tmp = rt.workspace(nbytes)
+        rt.check(rt.lib.nm_neighbor_index_dbscan(
+            rt.ctx, ctypes.byref(self.filter.nm_lattice), radius, min_weight, _device.ptr(self._work),
+            self._work.numel(), _device.ptr(voxel_class), _device.ptr(voxel_weight), min_size, _device.ptr(labels),
+            _device.ptr(sizes), _device.ptr(core), _device.ptr(density), _device.ptr(count), _device.ptr(tmp), nbytes,
+            rt.stream()))
+        if check_weight and voxel_weight is not None:
+            kept, negative = (int(x) for x in torch.stack((count[0], (voxel_weight < 0).any().to(torch.int64))).cpu())
+            if negative:
+                raise ValueError("voxel_weight must not be negative")
+        else:
+            kept = int(count[0])
+        if kept < 0:        # (cannot happen: the scratch was sized for this handle's M)
+            raise _ffi.NimrudHipError("nm_neighbor_index_dbscan: scratch too small for the index")
+        return labels, sizes[:kept], core.to(torch.bool), density
+
+    def dbscan(self, radius, min_weight, voxel_weight=None, voxel_class=None, min_size=1, return_density=False):
+        """(labels int64 (M,), sizes int64 (C,), core bool (M,)) and, with return_density, density int64 (M,): DBSCAN on
+        the voxel graph of components() - voxels u and v are neighbors when lists(voxels(), radius) names one for the
+        other and both carry the same voxel_class >= 0 (None: one class for all; a negative class takes the voxel out:
+        label -1, not core, density 0).  density[v] is the sum of voxel_weight (integers >= 0, (M,), e.g.
+        point_counts(); None counts voxels; a negative weight raises ValueError) over v itself and its neighbors, and v is a CORE voxel where density[v] >=
+        min_weight (sklearn's min_samples with sample_weight).  the clusters are the connected components of the core
+        voxels.  a voxel that is not core joins the cluster of its nearest core neighbor - by (squared distance as
+        lists() forms it, position), equal distances to the smaller position - as a BORDER voxel, and without a core
+        neighbor it is noise, label -1.  a cluster's size is the sum of the weights of its members, core and border;
+        clusters below min_size are dropped, their members get -1 and `core` stays.  kept clusters are numbered
+        0..C-1 in ascending order of their smallest core voxel position.  with voxel_weight None and min_weight <= 1
+        every voxel is core and (labels, sizes) are those of components().  the result is a function of the arguments
+        alone, the same bit for bit on every run."""
+        self._need_index("dbscan")
+        radius = float(radius)
+        if not radius >= 0.0:
+            raise ValueError("radius must be a number >= 0")
+        for name, value in (("min_weight", min_weight), ("min_size", min_size)):
+            if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+                raise ValueError("%s must be an integer" % name)
+        cls = None if voxel_class is None else self._voxel_integers(voxel_class, "voxel_class")
+        weight = None if voxel_weight is None else self._voxel_integers(voxel_weight, "voxel_weight")
+        out = self._dbscan_device(radius, int(min_weight), cls, weight, int(min_size), bool(return_density),
+                                  check_weight=True)
+        out = out if return_density else out[:3]
+        return out if self._as_torch else tuple(t.cpu().numpy() for t in out)
+
     def component_table(self, labels, voxel_weight=None):
         """fp64 (C, 25): segment_table over voxels() for the labels components() returned - one row of descriptors
         per component of the voxel graph (columns: SEGMENT_COLUMNS).  voxels with label -1 are in no segment.
@@ -703,6 +763,42 @@ def cluster_cloud(cloud, edge_length, radius, point_class=None, min_points=1):
     if isinstance(cloud, torch.Tensor):
         return point_labels, sizes
     return point_labels.cpu().numpy(), sizes.cpu().numpy()
+
+
+def dbscan_cloud(cloud, edge_length, radius, min_points, point_class=None, min_cluster_points=1):
+    """(point_labels int64 (N,), sizes int64 (C,), point_core bool (N,)): DBSCAN of a cloud in one call, on its voxels.
+    the cloud is voxel-filtered at `edge_length`, every voxel is weighted by the points in it (point_counts()), and
+    NeighborIndex.dbscan clusters the voxels: a voxel is core where the voxels within `radius` of its centre, itself
+    included, hold at least `min_points` POINTS.  every point takes the label and the core flag of its voxel.  sizes
+    and min_cluster_points count points too: clusters of fewer points are dropped, their points get -1.  clusters are
+    numbered 0..C-1 in ascending order of their smallest core voxel position.
+    point_class (integers, (N,); magnitudes below 2^53): a voxel's class is the MINIMUM class of the points in it, as
+    in cluster_cloud; density and links stay within a class, a negative class is out.
+    one NeighborIndex (method "index"), built and asked once.  torch in, torch out; numpy in, numpy out."""
+    index = NeighborIndex(cloud, edge_length, method="index")
+    rt = index._rt
+    for name, value in (("min_points", min_points), ("min_cluster_points", min_cluster_points)):
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+            raise ValueError("%s must be an integer" % name)
+    radius = float(radius)
+    if not radius >= 0.0:
+        raise ValueError("radius must be a number >= 0")
+    voxel_class = None
+    if point_class is not None:
+        column = _integer_column(point_class, index._search.shape[0], rt.device, "point_class", "point")
+        # min of an integer-valued fp64 column: exact
+        voxel_class = index.voxel_table(column.to(torch.float64), reduce="min")[:, 0].to(torch.int64)
+    weight = index._grouping()[0]
+    labels, sizes, core, _ = index._dbscan_device(radius, int(min_points), voxel_class, weight,
+                                                  int(min_cluster_points), False)
+    voxel = index._voxel_of_device(index._search)
+    inside = voxel >= 0
+    at = voxel.clamp(min=0)
+    point_labels = torch.where(inside, labels[at], torch.full_like(voxel, -1))
+    point_core = inside & core[at]
+    if isinstance(cloud, torch.Tensor):
+        return point_labels, sizes, point_core
+    return point_labels.cpu().numpy(), sizes.cpu().numpy(), point_core.cpu().numpy()
 
 
 # columns of a segment table (nm_segment_table): name -> slice
