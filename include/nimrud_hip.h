@@ -410,6 +410,53 @@ int nm_neighbor_index_dbscan(nm_ctx* ctx, const nm_lattice* lat, double radius, 
                              int64_t min_size, int64_t* d_label, int64_t* d_size, uint8_t* d_core,
                              int64_t* d_density, int64_t* d_count, void* d_tmp, size_t tmp_bytes, void* stream);
 
+/* ---- smoothness-constrained regions of the voxel graph (new symbols only: additive within ABI 7) ---------------
+ * region growing stated as connected components: the graph of nm_neighbor_index_components, where two voxels link
+ * only when their normals and, optionally, a row of per-voxel values agree - so a roof and the wall below it, a
+ * kerb and the road come out as regions of their own.  no list is written, nothing is sorted, no seed order.
+ *   graph: as nm_neighbor_index_components - u ~ v iff the lists name one for the other and both carry the same
+ *     class >= 0; a voxel of negative class is out of the graph: label -1.
+ *   seeds: d_seed[v] != 0 makes a voxel of the graph a seed; d_seed NULL makes every voxel of the graph one.  only
+ *     seeds link (the caller-supplied analogue of DBSCAN's core).
+ *   link rule: a graph edge between two seeds u, v links them iff both of
+ *     d_normal given:  fabs((nu.x*nv.x + nu.y*nv.y) + nu.z*nv.z) >= min_cos, unfused, in this order, on the rows
+ *       d_normal + v*normal_stride (doubles).  normals are unsigned directions: a sign flip across a wall does not
+ *       cut it.  normals are not normalised here.  the test is false for NaN: a NaN normal links nothing, a zero
+ *       normal links only where min_cos <= 0.
+ *     d_value given (dims > 0):  fabs(value_u[c] - value_v[c]) <= max_step[c] for every c < dims, on the rows
+ *       d_value + v*value_stride.  the limit is inclusive; NaN is false.  max_step is HOST memory, dims entries.
+ *     hold.  both tests are symmetric in (u, v) bit for bit - the products commute, fl(a - b) = -fl(b - a) - so
+ *     testing each edge once, from its smaller end, is the contract and not an approximation of it.
+ *   regions: the connected components of the seeds under the linked edges.  a voxel of the graph that is not a seed
+ *     joins the region of its NEAREST seed neighbor of its class, ordered by (d2 as the lists' test forms it, voxel
+ *     position) - DBSCAN's border rule; the link rule is not asked there, which is what puts the voxels of a crease
+ *     back onto a face.  without a seed neighbor it gets -1.
+ *   a region's size is the sum of d_weight (NULL = 1 each) over its members, seeds and attached voxels; regions
+ *     below min_size are dropped and their members get -1.  kept regions are numbered 0..C-1 in ascending order of
+ *     their smallest SEED position.
+ *   identities: with d_seed, d_normal NULL and dims 0, labels, sizes and d_count[0..1] are those of
+ *     nm_neighbor_index_components; with d_seed a nm_neighbor_index_dbscan call's d_core and no rule, labels and
+ *     sizes are those of that call.
+ *   output: d_label[M], d_size (room for M entries), d_count (int64[3]) = {C = regions kept, regions before
+ *     min_size, seeds in the graph}.  all of it is a function of the arguments alone, the same bit for bit on every
+ *     run.
+ *   d_tmp: nm_neighbor_index_regions_workspace_bytes(M) bytes (16-byte aligned), the size of the dbscan scratch;
+ *     the query needs no GPU, is monotone in M and 0 for M < 0 or M >= 2^31.  a d_tmp that takes the minimum (the
+ *     query at 0) but not this index's M labels nothing and sets d_count to {-1, -1, -1}.
+ *   errors, all before anything is queued: NM_ERR_INVALID for a null output or lattice, a NaN or negative radius,
+ *     dims outside [0, NM_REGION_MAX_DIMS], dims > 0 without d_value or max_step or with value_stride < dims, a
+ *     NaN or negative max_step[c], and with d_normal given a normal_stride < 3 or a NaN min_cos; NM_ERR_RADIUS as
+ *     nm_neighbor_index_lists, NM_ERR_WORKSPACE for too small a d_work or a d_tmp below the minimum, NM_ERR_LATTICE
+ *     as every entry point that takes the index.  nothing here waits for the device. */
+#define NM_REGION_MAX_DIMS 4
+size_t nm_neighbor_index_regions_workspace_bytes(int64_t n_voxels);
+int nm_neighbor_index_regions(nm_ctx* ctx, const nm_lattice* lat, double radius, const void* d_work,
+                              size_t work_bytes, const int64_t* d_class, const int64_t* d_weight,
+                              const uint8_t* d_seed, const double* d_normal, int64_t normal_stride, double min_cos,
+                              const double* d_value, int64_t value_stride, int32_t dims, const double* max_step,
+                              int64_t min_size, int64_t* d_label, int64_t* d_size, int64_t* d_count, void* d_tmp,
+                              size_t tmp_bytes, void* stream);
+
 /* ---- per-segment descriptors of a labelled cloud (new symbols only: additive within ABI 7) --------------------
  * what a cluster is as an object: how many points, where, its box, its shape and which way it points.  the last
  * stage behind a classifier and nm_neighbor_index_components; the table is a plain fp64 feature matrix.

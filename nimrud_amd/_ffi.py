@@ -24,6 +24,7 @@ NM_COMM_ID_BYTES = 128
 ABI_VERSION = 7
 NM_STATS_MAX_DIMS = 16
 NM_NEAREST_MAX_K = 32
+NM_REGION_MAX_DIMS = 4
 NM_SEGMENT_COLUMNS = 25
 NM_SEGMENT_CHUNK = 256
 NM_REDUCE = {"mean": 0, "sum": 1, "min": 2, "max": 3}      # NM_REDUCE_MEAN .. NM_REDUCE_MAX
@@ -130,6 +131,11 @@ SIGNATURES = {
     "nm_neighbor_index_dbscan": (ctypes.c_int,
                                  [c_ptr, _LATP, c_f64, c_i64, c_ptr, c_size, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr,
                                   c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "nm_neighbor_index_regions_workspace_bytes": (c_size, [c_i64]),
+    "nm_neighbor_index_regions": (ctypes.c_int,
+                                  [c_ptr, _LATP, c_f64, c_ptr, c_size, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_f64,
+                                   c_ptr, c_i64, c_i32, ctypes.POINTER(c_f64), c_i64, c_ptr, c_ptr, c_ptr, c_ptr,
+                                   c_size, c_ptr]),
     "nm_segment_table_workspace_bytes": (c_size, [c_i64, c_i64]),
     "nm_segment_table": (ctypes.c_int,
                          [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_size, c_ptr]),

@@ -1321,6 +1321,86 @@ __global__ __launch_bounds__(256) void k_db_border(const int64_t* __restrict__ a
         atomicAdd((unsigned long long*)(d_count + 2), (unsigned long long)__popcll(cores));
 }
 
+// ---- regions: smoothness-constrained region growing on the same graph ---------------------------------------------------
+// dbscan's shape with the caller's seeds in the place of the core voxels and a predicate on every seed-seed edge: the
+// regions are the components of the seeds under the edges whose two normals and value rows agree.  eff[] = the class
+// of a seed of the graph and -1 for every other voxel (k_rg_seed); k_cc_init on eff[]; k_rg_link, k_cc_link's sibling
+// with the predicate between the class test and the join; k_db_border as it is - a voxel of the graph that is no seed
+// joins the region of its nearest seed neighbor by (d2, position), the predicate is not asked there - and flatten,
+// mark, scan and label as for components.  tmp: dbscan's layout (DbPlan).
+//
+// both tests are symmetric in (u, v) bit for bit - the three products commute and the sum keeps its order,
+// fl(a - b) = -fl(b - a) and fabs drops the sign - so the forward walk, which sees an edge from its smaller end
+// only, decides exactly what the larger end would have decided
+struct RgStep {
+    double s[NM_REGION_MAX_DIMS];
+};
+
+__global__ __launch_bounds__(256) void k_rg_seed(const uint32_t* __restrict__ index_header, uint32_t room,
+                                                 const int64_t* __restrict__ cls, const uint8_t* __restrict__ seed,
+                                                 int64_t* __restrict__ eff, int64_t* __restrict__ d_count)
+{
+    const uint32_t m = cc_voxels(index_header, room);
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v == 0) d_count[2] = 0;          // (the seeds are counted by k_db_border)
+    if (v >= m) return;
+    const int64_t c = cls ? cls[v] : 0;
+    eff[v] = (c >= 0 && (!seed || seed[v])) ? c : -1;
+}
+
+// link: one lane per seed, its own normal and value row in registers for the whole walk.  per hit, cheapest first:
+// the 8 bytes of eff[u] (seed and same class in one load), the DIMS value columns, the 24 bytes of the normal; a hit
+// that fails touches no word of parent[].  the comparisons are written so that NaN is false
+template <bool NORMAL, int DIMS>
+__global__ __launch_bounds__(256) void k_rg_link(const int64_t* __restrict__ addr,
+                                                 const uint32_t* __restrict__ index_header, uint32_t room,
+                                                 const uint32_t* __restrict__ leaf,
+                                                 const uint32_t* __restrict__ rank, LatticeDev L, double r2,
+                                                 int32_t dmin, int32_t W, const int64_t* __restrict__ eff,
+                                                 const double* __restrict__ normal, int64_t normal_stride,
+                                                 double min_cos, const double* __restrict__ value,
+                                                 int64_t value_stride, RgStep step, uint32_t* parent)
+{
+    const uint32_t m = cc_voxels(index_header, room);
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= m) return;
+    const int64_t c = eff[v];
+    if (c < 0) return;
+    const int64_t a = addr[v];
+    const int32_t ox = (int32_t)(a & (((int64_t)1 << L.wx) - 1));
+    const int32_t oy = (int32_t)((a >> L.s0) & (((int64_t)1 << L.wy) - 1));
+    const int32_t oz = (int32_t)(a >> L.s1);
+    double nx = 0.0, ny = 0.0, nz = 0.0;
+    if constexpr (NORMAL) {
+        const double* n = normal + (int64_t)v * normal_stride;
+        nx = n[0];
+        ny = n[1];
+        nz = n[2];
+    }
+    double own[DIMS > 0 ? DIMS : 1];
+    if constexpr (DIMS > 0) {
+        const double* x = value + (int64_t)v * value_stride;
+#pragma unroll
+        for (int k = 0; k < DIMS; ++k) own[k] = x[k];
+    }
+    uint32_t mine = v;       // (as k_cc_link)
+    nbr_walk_forward(ox, oy, oz, leaf, rank, L, r2, dmin, W, [&](uint32_t u) {
+        if (eff[u] != c) return;
+        if constexpr (DIMS > 0) {
+            const double* x = value + (int64_t)u * value_stride;
+            bool near = true;
+#pragma unroll
+            for (int k = 0; k < DIMS; ++k) near = near && fabs(own[k] - x[k]) <= step.s[k];
+            if (!near) return;
+        }
+        if constexpr (NORMAL) {
+            const double* n = normal + (int64_t)u * normal_stride;
+            if (!(fabs((nx * n[0] + ny * n[1]) + nz * n[2]) >= min_cos)) return;
+        }
+        mine = cc_join(parent, mine, u);
+    });
+}
+
 // argument checks shared by the entry points that take a built workspace
 int nbr_check_index(nm_ctx* ctx, const char* who, const nm_lattice* lat, const void* d_work, size_t work_bytes,
                     LatticeDev* L, NbrPlan* P)
@@ -1740,6 +1820,115 @@ extern "C" int nm_neighbor_index_dbscan(nm_ctx* ctx, const nm_lattice* lat, doub
     // the core clusters: components on the effective classes
     k_cc_init<<<blocks, 256, 0, s>>>(index_header, room, eff, parent, keep, size, d_count);
     k_cc_link<<<blocks, 256, 0, s>>>(addr, index_header, room, leaf, rank, L, r2, dmin, W, eff, parent);
+    k_db_border<<<blocks, 256, 0, s>>>(addr, index_header, room, leaf, rank, L, r2, dmin, W, d_class, eff, parent,
+                                       d_count);
+    k_cc_flatten<<<(unsigned)(C.room / CC_FLAT_THREADS), CC_FLAT_THREADS, 0, s>>>(index_header, room, d_weight,
+                                                                                  parent, size);
+    k_cc_mark<<<blocks, 256, 0, s>>>(index_header, room, parent, size, min_size, keep, d_count);
+    k_nbr_scan_reduce<<<C.scan_blocks, NBR_SCAN_THREADS, 0, s>>>(keep, C.tiles_per_block, C.room, partial);
+    k_nbr_scan_apply<<<C.scan_blocks, NBR_SCAN_THREADS, 0, s>>>(keep, C.tiles_per_block, C.room, partial, header,
+                                                                d_count);
+    k_cc_label<<<blocks, 256, 0, s>>>(index_header, room, parent, size, min_size, keep, d_label, d_size, d_count);
+    NM_HIP(ctx, hipGetLastError());
+    return NM_OK;
+}
+
+// ---- smoothness-constrained regions of the voxel graph (additive within ABI 7) ------------------------------------------
+
+extern "C" size_t nm_neighbor_index_regions_workspace_bytes(int64_t n_voxels)
+{
+    if (n_voxels < 0 || n_voxels >= (int64_t)1 << 31) return 0;
+    return db_plan(n_voxels).bytes;
+}
+
+namespace {
+
+template <bool NORMAL>
+void rg_launch_link(int32_t dims, unsigned blocks, hipStream_t s, const int64_t* addr, const uint32_t* index_header,
+                    uint32_t room, const uint32_t* leaf, const uint32_t* rank, const LatticeDev& L, double r2,
+                    int32_t dmin, int32_t W, const int64_t* eff, const double* normal, int64_t normal_stride,
+                    double min_cos, const double* value, int64_t value_stride, const RgStep& step, uint32_t* parent)
+{
+#define RG_LINK(D)                                                                                                   \
+    k_rg_link<NORMAL, D><<<blocks, 256, 0, s>>>(addr, index_header, room, leaf, rank, L, r2, dmin, W, eff, normal,  \
+                                                normal_stride, min_cos, value, value_stride, step, parent)
+    switch (dims) {
+    case 0: RG_LINK(0); break;
+    case 1: RG_LINK(1); break;
+    case 2: RG_LINK(2); break;
+    case 3: RG_LINK(3); break;
+    default: RG_LINK(4); break;
+    }
+#undef RG_LINK
+}
+
+}  // namespace
+
+extern "C" int nm_neighbor_index_regions(nm_ctx* ctx, const nm_lattice* lat, double radius, const void* d_work,
+                                         size_t work_bytes, const int64_t* d_class, const int64_t* d_weight,
+                                         const uint8_t* d_seed, const double* d_normal, int64_t normal_stride,
+                                         double min_cos, const double* d_value, int64_t value_stride, int32_t dims,
+                                         const double* max_step, int64_t min_size, int64_t* d_label,
+                                         int64_t* d_size, int64_t* d_count, void* d_tmp, size_t tmp_bytes,
+                                         void* stream)
+{
+    NM_ENTER_STREAM(ctx, stream);
+    if (!d_label || !d_size || !d_count) NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_regions: bad arguments");
+    if (!(radius >= 0.0))      // (NaN fails)
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_regions: radius must be >= 0");
+    if (dims < 0 || dims > NM_REGION_MAX_DIMS)
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_regions: dims = %d outside [0, %d]", dims,
+                NM_REGION_MAX_DIMS);
+    if (dims > 0 && (!d_value || !max_step || value_stride < dims))
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_regions: %d value columns need d_value, max_step and a "
+                "stride of at least %d", dims, dims);
+    if (d_normal && (normal_stride < 3 || min_cos != min_cos))
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_regions: normals need a stride of at least 3 and a min_cos "
+                "that is a number");
+    RgStep step = {};
+    for (int32_t k = 0; k < dims; ++k) {
+        if (!(max_step[k] >= 0.0))      // (NaN fails)
+            NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_regions: max_step[%d] must be >= 0", k);
+        step.s[k] = max_step[k];
+    }
+    LatticeDev L;
+    NbrPlan P;
+    int rc = nbr_check_index(ctx, "nm_neighbor_index_regions", lat, d_work, work_bytes, &L, &P);
+    if (rc) return rc;
+    int32_t dmin = 0;
+    const int W = nbr_candidate_width(radius, lat->edge, &dmin);
+    if (W < 0) NM_FAIL(ctx, NM_ERR_RADIUS, "radius/edge ratio outside the supported range");
+    if (!d_tmp || tmp_bytes < db_plan(0).bytes)
+        NM_FAIL(ctx, NM_ERR_WORKSPACE, "nm_neighbor_index_regions: temporary workspace too small");
+    const DbPlan D = db_plan_of(tmp_bytes);
+    const CcPlan& C = D.C;
+    hipStream_t s = (hipStream_t)stream;
+    const char* w = (const char*)d_work;
+    const uint32_t* index_header = (const uint32_t*)w;
+    const uint32_t* leaf = (const uint32_t*)(w + P.off_leaf);
+    const uint32_t* rank = (const uint32_t*)(w + P.off_rank);
+    char* t = (char*)d_tmp;
+    uint32_t* header = (uint32_t*)t;
+    uint32_t* partial = (uint32_t*)(t + C.off_partial);
+    int64_t* addr = (int64_t*)(t + C.off_addr);
+    int64_t* size = (int64_t*)(t + C.off_size);
+    uint32_t* parent = (uint32_t*)(t + C.off_parent);
+    uint32_t* keep = (uint32_t*)(t + C.off_keep);
+    int64_t* eff = (int64_t*)(t + D.off_eff);
+    const uint32_t room = (uint32_t)C.room;
+    const unsigned blocks = (unsigned)(C.room / 256);
+    const uint64_t words = P.superblocks * NM_LEAF_WORDS;
+    const double r2 = radius * radius;
+    k_nbr_addresses<<<(unsigned)((words + 255) / 256), 256, 0, s>>>(leaf, rank, index_header, L, words, addr, room);
+    k_rg_seed<<<blocks, 256, 0, s>>>(index_header, room, d_class, d_seed, eff, d_count);
+    // the regions of the seeds: components on the effective classes, under the edges the predicate lets through
+    k_cc_init<<<blocks, 256, 0, s>>>(index_header, room, eff, parent, keep, size, d_count);
+    if (d_normal)
+        rg_launch_link<true>(dims, blocks, s, addr, index_header, room, leaf, rank, L, r2, dmin, W, eff, d_normal,
+                             normal_stride, min_cos, d_value, value_stride, step, parent);
+    else
+        rg_launch_link<false>(dims, blocks, s, addr, index_header, room, leaf, rank, L, r2, dmin, W, eff, nullptr, 0,
+                              0.0, d_value, value_stride, step, parent);
     k_db_border<<<blocks, 256, 0, s>>>(addr, index_header, room, leaf, rank, L, r2, dmin, W, d_class, eff, parent,
                                        d_count);
     k_cc_flatten<<<(unsigned)(C.room / CC_FLAT_THREADS), CC_FLAT_THREADS, 0, s>>>(index_header, room, d_weight,

@@ -20,6 +20,7 @@ occupancy index -> fused search/moments/eigen kernel.  see DESIGN.md.
 """
 
 import ctypes
+import math
 import time
 
 import numpy as np
@@ -299,6 +300,9 @@ class NeighborIndex(object):
                                 connected components of the graph lists(voxels(), radius) spans, without the lists
         .dbscan(radius, min_weight, voxel_weight=None, ...) -> (labels (M,), sizes (C,), core (M,)): components of the
                                 dense (core) voxels only, border voxels attached, the rest noise (-1)
+        .regions(radius, voxel_normal=None, max_angle=None, voxel_value=None, max_step=None, voxel_seed=None, ...)
+                                -> (labels (M,), sizes (C,), seed (M,)): region growing - components of the seed
+                                voxels under the edges whose normals / values agree, the other voxels attached
         .component_table(labels, voxel_weight=None) -> (C, 25): one row of descriptors per component (segment_table
                                 over voxels())
     torch in, torch out; numpy in, numpy out (addresses / voxels / point_counts / members / components / dbscan follow the
@@ -675,6 +679,108 @@ class NeighborIndex(object):
         out = out if return_density else out[:3]
         return out if self._as_torch else tuple(t.cpu().numpy() for t in out)
 
+    def _voxel_rows(self, values, what, most):
+        """a per-voxel fp64 table as a device tensor (M, D <= most) with unit column stride (a row stride is kept)"""
+        t = torch.as_tensor(values)
+        if not t.dtype.is_floating_point:
+            raise ValueError("%s must have a floating-point dtype" % what)
+        t = t.to(device=self._rt.device, dtype=torch.float64)
+        if t.ndim == 1:
+            t = t.reshape(-1, 1)
+        if t.ndim != 2 or t.shape[0] != self.n_voxels:
+            raise ValueError("%s must have one row per voxel" % what)
+        if not 1 <= t.shape[1] <= most:
+            raise ValueError("%s must have between 1 and %d columns" % (what, most))
+        return _unit_columns(t)
+
+    def _regions_device(self, radius, normal, min_cos, value, max_step, seed, voxel_class, voxel_weight, min_size):
+        """enqueue nm_neighbor_index_regions on device tensors (or None) - normal fp64 (M, >= 3), value fp64 (M, D),
+        seed uint8 (M,), class and weight int64 (M,); max_step: D host floats - (labels, sizes, seed bool: the seeds
+        in the graph); one host read, of the counts"""
+        rt = self._rt
+        m = self.n_voxels
+        labels = torch.empty(m, dtype=torch.int64, device=rt.device)
+        sizes = torch.empty(max(m, 1), dtype=torch.int64, device=rt.device)
+        in_graph = torch.ones(m, dtype=torch.bool, device=rt.device) if voxel_class is None else voxel_class >= 0
+        is_seed = in_graph if seed is None else in_graph & (seed != 0)
+        if m == 0:
+            return labels, sizes[:0], is_seed
+        dims = 0 if value is None else int(value.shape[1])
+        steps = (ctypes.c_double * max(dims, 1))(*[float(s) for s in max_step])
+        count = torch.empty(3, dtype=torch.int64, device=rt.device)
+        nbytes = int(rt.lib.nm_neighbor_index_regions_workspace_bytes(m))
+        tmp = rt.workspace(nbytes)
+        rt.check(rt.lib.nm_neighbor_index_regions(
+            rt.ctx, ctypes.byref(self.filter.nm_lattice), radius, _device.ptr(self._work), self._work.numel(),
+            _device.ptr(voxel_class), _device.ptr(voxel_weight), _device.ptr(seed), _device.ptr(normal),
+            _device.row_stride(normal) if normal is not None else 0, min_cos, _device.ptr(value),
+            _device.row_stride(value) if value is not None else 0, dims, steps, min_size, _device.ptr(labels),
+            _device.ptr(sizes), _device.ptr(count), _device.ptr(tmp), nbytes, rt.stream()))
+        kept = int(count[0])
+        if kept < 0:        # (cannot happen: the scratch was sized for this handle's M)
+            raise _ffi.NimrudHipError("nm_neighbor_index_regions: scratch too small for the index")
+        return labels, sizes[:kept], is_seed
+
+    def regions(self, radius, voxel_normal=None, max_angle=None, voxel_value=None, max_step=None, voxel_seed=None,
+                voxel_class=None, voxel_weight=None, min_size=1):
+        """(labels int64 (M,), sizes int64 (C,), seed bool (M,)): region growing under a smoothness constraint, stated
+        as connected components - the voxel graph of components() (voxels u and v are neighbors when lists(voxels(),
+        radius) names one for the other and both carry the same voxel_class >= 0), in which only SEEDS link, and two
+        neighboring seeds link only when both of these hold:
+          voxel_normal (fp64 (M, 3)) and max_angle (radians) given: fabs(dot(n_u, n_v)) >= cos(max_angle), the dot
+            product as (x*x + y*y) + z*z, unfused.  normals are unsigned directions and are not normalised here; a
+            NaN normal links nothing, a zero normal only where cos(max_angle) <= 0.
+          voxel_value ((M,) or (M, D), D <= 4) and max_step (a scalar or (D,), >= 0) given: fabs(value_u[c] -
+            value_v[c]) <= max_step[c] in every column, inclusive; NaN is false.
+        voxel_seed (bool or integers, (M,)): non-zero makes a voxel of the graph a seed; None: every voxel of the
+        graph.  the regions are the connected components of the seeds under the linked edges.  a voxel of the graph
+        that is no seed joins the region of its nearest seed neighbor of its class - by (squared distance as lists()
+        forms it, position), the rule above is not asked - and without one it gets -1.  a region's size is the sum
+        of voxel_weight (integers, (M,); None counts voxels) over all its members; regions below min_size are
+        dropped, their members get -1.  kept regions are numbered 0..C-1 in ascending order of their smallest seed
+        position.  `seed` returns the seeds in the graph.  without seeds and rules this is components(); with a
+        dbscan() call's core as voxel_seed and no rule, that call's labels and sizes.  the result is a function of
+        the arguments alone, the same bit for bit on every run (PCL's RegionGrowing depends on its seed order)."""
+        self._need_index("regions")
+        radius = float(radius)
+        if not radius >= 0.0:
+            raise ValueError("radius must be a number >= 0")
+        if isinstance(min_size, bool) or not isinstance(min_size, (int, np.integer)):
+            raise ValueError("min_size must be an integer")
+        if (voxel_normal is None) != (max_angle is None):
+            raise ValueError("voxel_normal and max_angle go together: give both or neither")
+        if (voxel_value is None) != (max_step is None):
+            raise ValueError("voxel_value and max_step go together: give both or neither")
+        normal, min_cos = None, 0.0
+        if voxel_normal is not None:
+            max_angle = float(max_angle)
+            if max_angle != max_angle:
+                raise ValueError("max_angle must be a number (radians)")
+            min_cos = _min_cos(max_angle)
+            normal = self._voxel_rows(voxel_normal, "voxel_normal", 3)
+            if normal.shape[1] != 3:
+                raise ValueError("voxel_normal must be (M, 3)")
+        value, steps = None, ()
+        if voxel_value is not None:
+            value = self._voxel_rows(voxel_value, "voxel_value", _ffi.NM_REGION_MAX_DIMS)
+            dims = int(value.shape[1])
+            steps = np.asarray(max_step, dtype=np.float64)
+            if steps.ndim == 0:
+                steps = np.full(dims, float(steps))
+            if steps.shape != (dims,) or not (steps >= 0.0).all():      # (NaN fails)
+                raise ValueError("max_step must be a number >= 0, or one per column of voxel_value")
+        seed = None
+        if voxel_seed is not None:
+            if isinstance(voxel_seed, torch.Tensor) and voxel_seed.dtype == torch.bool:
+                voxel_seed = voxel_seed.to(torch.uint8)
+            elif not isinstance(voxel_seed, torch.Tensor) and np.asarray(voxel_seed).dtype == np.bool_:
+                voxel_seed = np.asarray(voxel_seed).astype(np.uint8)
+            seed = (self._voxel_integers(voxel_seed, "voxel_seed") != 0).to(torch.uint8)
+        cls = None if voxel_class is None else self._voxel_integers(voxel_class, "voxel_class")
+        weight = None if voxel_weight is None else self._voxel_integers(voxel_weight, "voxel_weight")
+        out = self._regions_device(radius, normal, min_cos, value, steps, seed, cls, weight, int(min_size))
+        return out if self._as_torch else tuple(t.cpu().numpy() for t in out)
+
     def component_table(self, labels, voxel_weight=None):
         """fp64 (C, 25): segment_table over voxels() for the labels components() returned - one row of descriptors
         per component of the voxel graph (columns: SEGMENT_COLUMNS).  voxels with label -1 are in no segment.
@@ -688,6 +794,13 @@ class NeighborIndex(object):
         centres = self.filter.address_to_coordinate(self._addresses_device())
         table = _segment_table_device(rt, centres, label, weight, None)
         return table if self._as_torch else table.cpu().numpy()
+
+
+def _min_cos(max_angle):
+    """the cosine regions() compares fabs(dot) with: cos(max_angle), and 0 from a right angle on - unsigned directions
+    are never further apart, but the float pi/2 lies below the real one and its cosine, 6e-17, would still cut normals
+    that are perpendicular exactly"""
+    return math.cos(max_angle) if max_angle < math.pi / 2 else 0.0
 
 
 def _integer_column(values, n, device, what, per):
@@ -799,6 +912,66 @@ def dbscan_cloud(cloud, edge_length, radius, min_points, point_class=None, min_c
     if isinstance(cloud, torch.Tensor):
         return point_labels, sizes, point_core
     return point_labels.cpu().numpy(), sizes.cpu().numpy(), point_core.cpu().numpy()
+
+
+def voxel_normals(index, radius, max_curvature=None):
+    """(normals fp64 (M, 3), seed bool (M,)) on the device: what smooth_regions hands to NeighborIndex.regions.  the
+    normal of a voxel is process_gpu_normals' at its centre over the handle's own search cloud, one scale at the
+    handle's edge length and `radius`; its surface variation is 1 - (f[:, 2] + f[:, 3]) of the same call's features,
+    the smallest eigenvalue's share of the sum.  a voxel is a seed where the normal is not zero (three voxels or more
+    in reach) and, with max_curvature given, where the variation is <= max_curvature."""
+    index._need_index("voxel_normals")
+    centres = index.filter.address_to_coordinate(index._addresses_device())
+    edge = float(index.filter.edge_length)
+    features, normals = process_gpu_normals(centres, index._search, [edge], [float(radius)])
+    seed = (normals != 0.0).any(dim=1)
+    if max_curvature is not None:
+        seed = seed & ((1.0 - (features[:, 2] + features[:, 3])) <= float(max_curvature))
+    return normals, seed
+
+
+def smooth_regions(cloud, edge_length, radius, max_angle, normal_radius=None, max_curvature=None, point_class=None,
+                   min_points=1):
+    """(point_labels int64 (N,), sizes int64 (C,), table fp64 (C, 25)): the smooth surfaces of a cloud in one call -
+    planes and gently curved faces come out as regions of their own where cluster_cloud and dbscan_cloud see one blob.
+    the cloud is voxel-filtered at `edge_length`; every voxel gets a normal and a surface variation from the voxels
+    within `normal_radius` (None: `radius`) of its centre (voxel_normals); voxels with a normal - and, with
+    max_curvature given, a variation <= max_curvature - are seeds; NeighborIndex.regions links neighboring seeds
+    whose normals differ by at most `max_angle` radians, and hangs every other voxel (a crease, an edge) onto its
+    nearest seed neighbor.  every point takes the label of its voxel.  sizes and min_points count POINTS; regions of
+    fewer points are dropped, their points get -1.  table is segment_table over the points (SEGMENT_COLUMNS): its
+    normal column is the fitted normal of each region, table[:, 0] == sizes.  point_class as in cluster_cloud.
+    one NeighborIndex (method "index"); the cloud is uploaded once.  torch in, torch out; numpy in, numpy out."""
+    rt, points = _device.as_cloud(cloud)
+    index = NeighborIndex(points, edge_length, method="index")
+    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)):
+        raise ValueError("min_points must be an integer")
+    radius = float(radius)
+    if not radius >= 0.0:
+        raise ValueError("radius must be a number >= 0")
+    normal_radius = radius if normal_radius is None else float(normal_radius)
+    if not normal_radius >= 0.0:
+        raise ValueError("normal_radius must be a number >= 0")
+    max_angle = float(max_angle)
+    if max_angle != max_angle:
+        raise ValueError("max_angle must be a number (radians)")
+    if max_curvature is not None and not float(max_curvature) >= 0.0:
+        raise ValueError("max_curvature must be a number >= 0")
+    voxel_class = None
+    if point_class is not None:
+        column = _integer_column(point_class, points.shape[0], rt.device, "point_class", "point")
+        # min of an integer-valued fp64 column: exact
+        voxel_class = index.voxel_table(column.to(torch.float64), reduce="min")[:, 0].to(torch.int64)
+    weight = index._grouping()[0]
+    normals, seed = voxel_normals(index, normal_radius, max_curvature)
+    labels, sizes, _ = index._regions_device(radius, normals, _min_cos(max_angle), None, (), seed.to(torch.uint8),
+                                             voxel_class, weight, int(min_points))
+    voxel = index._voxel_of_device(points)
+    point_labels = torch.where(voxel >= 0, labels[voxel.clamp(min=0)], torch.full_like(voxel, -1))
+    table = _segment_table_device(rt, points, point_labels, None, int(sizes.shape[0]))
+    if isinstance(cloud, torch.Tensor):
+        return point_labels, sizes, table
+    return point_labels.cpu().numpy(), sizes.cpu().numpy(), table.cpu().numpy()
 
 
 # columns of a segment table (nm_segment_table): name -> slice
