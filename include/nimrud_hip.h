@@ -457,6 +457,60 @@ int nm_neighbor_index_regions(nm_ctx* ctx, const nm_lattice* lat, double radius,
                               int64_t min_size, int64_t* d_label, int64_t* d_size, int64_t* d_count, void* d_tmp,
                               size_t tmp_bytes, void* stream);
 
+/* ---- peak-seeking segments of the voxel graph: hill climbing (new symbols only: additive within ABI 7) ---------
+ * components, dbscan and regions are connectivity rules: two objects of one kind that touch - interlocking tree
+ * crowns, cars parked bumper to bumper, two density modes joined by a thick bridge - come out as one.  here every
+ * voxel takes ONE uphill link, to a neighbor with a higher value, and a segment is everything that climbs to the same
+ * peak: crown delineation with height as the value, quick shift with a density as the value and NM_CLIMB_NEAREST.
+ * no list is written, nothing is sorted, no atomics in the link step: every voxel writes its own link only.
+ *   graph: as nm_neighbor_index_components - u ~ v iff the lists, asked with the voxel centres as queries, name one
+ *     for the other (((dx*dx + dy*dy) + dz*dz) <= r*r, inclusive; a voxel is its own neighbor at d2 = 0) and both
+ *     carry the same class.  a voxel v is IN THE GRAPH iff its class is >= 0 (d_class NULL = class 0 for all) and
+ *     d_value[v] is not NaN; a voxel outside the graph gets label -1 and link -1 and is nobody's candidate.
+ *   d_value (fp64[M], contiguous): the height every voxel climbs on.  +-inf are values like any other.
+ *   higher(u, v) := value[u] > value[v] || (value[u] == value[v] && u < v), u and v voxel positions.  on the voxels
+ *     of the graph this is a strict total order: equal values (-0 == +0) are ordered by the SMALLER position, and
+ *     higher(v, v) is false.  every comparison is false for NaN.
+ *   candidates: for v in the graph, a neighbor u is a candidate iff class[u] == class[v], value[u] is not NaN and
+ *     higher(u, v).  link[v] is chosen among the candidates, d2 being the squared distance of the two centres as the
+ *     lists' test forms it, ((dx*dx + dy*dy) + dz*dz) with d = centre(v) - centre(u), unfused:
+ *       NM_CLIMB_HIGHEST (steepest ascent): the largest value[u]; among equal values the smaller d2; among equal d2
+ *         the smaller position.
+ *       NM_CLIMB_NEAREST (quick shift): the smallest d2; among equal d2 the larger value[u]; then the smaller
+ *         position.
+ *     a voxel of the graph without a candidate is a PEAK: link[v] = v.  links strictly ascend in a strict total
+ *     order, so they form a forest whose roots are the peaks: no cycle, whatever the values.
+ *   segments: v belongs to the peak its links lead to.  a plateau of equal values climbs towards its smallest
+ *     position as far as the radius lets it: a plateau that is not convex at that radius may split into several
+ *     peaks.  every segment lies inside one component of nm_neighbor_index_components of the same radius and
+ *     classes.  a strictly increasing map of the values that keeps equal values equal changes nothing.
+ *   d_weight (int64[M], may be NULL = 1 each): a segment's size is the sum of the weights of its members, the peak
+ *     included; segments below min_size are dropped and their members get -1.  kept segments are numbered 0..C-1
+ *     in ascending order of their PEAK's position.
+ *   output: d_label[M]; d_size (room for M entries), d_size[c] the size of segment c; d_peak (room for M entries),
+ *     d_peak[c] the position of segment c's peak, ascending; d_link[M] (may be NULL: not wanted) the uphill link
+ *     of every voxel, the voxel itself at a peak, -1 outside the graph - written before anything is merged, so it
+ *     does not depend on d_weight or min_size; d_count (int64[2]) = {C = segments kept, peaks before min_size}.
+ *     entries of d_size and d_peak from C on are not touched.  all of it is a function of the arguments alone,
+ *     the same bit for bit on every run.
+ *   d_tmp: nm_neighbor_index_hill_climb_workspace_bytes(M) bytes (16-byte aligned), the size of the components
+ *     scratch; the query needs no GPU, is monotone in M and 0 for M < 0 or M >= 2^31.  a d_tmp that takes the
+ *     minimum (the query at 0) but not this index's M writes no label, size, peak or link and sets d_count to
+ *     {-1, -1}.
+ *   cost: one full-window walk per voxel, then the flatten, number and label steps of the components call; the
+ *     flatten step follows every voxel's chain of links to its peak, so its time grows with the longest chain.
+ *   errors, all before anything is queued: NM_ERR_INVALID for a null d_value, d_label, d_size, d_peak, d_count or
+ *     lattice, a mode other than the two, a NaN or negative radius; NM_ERR_RADIUS as nm_neighbor_index_lists,
+ *     NM_ERR_WORKSPACE for too small a d_work or a d_tmp below the minimum, NM_ERR_LATTICE as every entry point
+ *     that takes the index.  nothing here waits for the device. */
+enum { NM_CLIMB_HIGHEST = 0, NM_CLIMB_NEAREST = 1 };
+size_t nm_neighbor_index_hill_climb_workspace_bytes(int64_t n_voxels);
+int nm_neighbor_index_hill_climb(nm_ctx* ctx, const nm_lattice* lat, double radius, int32_t mode,
+                                 const void* d_work, size_t work_bytes, const double* d_value,
+                                 const int64_t* d_class, const int64_t* d_weight, int64_t min_size,
+                                 int64_t* d_label, int64_t* d_size, int64_t* d_peak, int64_t* d_link,
+                                 int64_t* d_count, void* d_tmp, size_t tmp_bytes, void* stream);
+
 /* ---- per-segment descriptors of a labelled cloud (new symbols only: additive within ABI 7) --------------------
  * what a cluster is as an object: how many points, where, its box, its shape and which way it points.  the last
  * stage behind a classifier and nm_neighbor_index_components; the table is a plain fp64 feature matrix.

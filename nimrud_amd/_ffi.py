@@ -25,6 +25,7 @@ ABI_VERSION = 7
 NM_STATS_MAX_DIMS = 16
 NM_NEAREST_MAX_K = 32
 NM_REGION_MAX_DIMS = 4
+NM_CLIMB = {"highest": 0, "nearest": 1}                    # NM_CLIMB_HIGHEST, NM_CLIMB_NEAREST
 NM_SEGMENT_COLUMNS = 25
 NM_SEGMENT_CHUNK = 256
 NM_REDUCE = {"mean": 0, "sum": 1, "min": 2, "max": 3}      # NM_REDUCE_MEAN .. NM_REDUCE_MAX
@@ -136,6 +137,10 @@ SIGNATURES = {
                                   [c_ptr, _LATP, c_f64, c_ptr, c_size, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_f64,
                                    c_ptr, c_i64, c_i32, ctypes.POINTER(c_f64), c_i64, c_ptr, c_ptr, c_ptr, c_ptr,
                                    c_size, c_ptr]),
+    "nm_neighbor_index_hill_climb_workspace_bytes": (c_size, [c_i64]),
+    "nm_neighbor_index_hill_climb": (ctypes.c_int,
+                                     [c_ptr, _LATP, c_f64, c_i32, c_ptr, c_size, c_ptr, c_ptr, c_ptr, c_i64, c_ptr,
+                                      c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "nm_segment_table_workspace_bytes": (c_size, [c_i64, c_i64]),
     "nm_segment_table": (ctypes.c_int,
                          [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_size, c_ptr]),

@@ -1401,6 +1401,93 @@ __global__ __launch_bounds__(256) void k_rg_link(const int64_t* __restrict__ add
     });
 }
 
+// ---- hill climbing: peak-seeking segments of the same graph ------------------------------------------------------------
+// every voxel of the graph takes ONE uphill link - a neighbor of its class that is higher than itself - or none, a
+// peak; a segment is everything that climbs to the same peak.  no union-find: the links ARE the forest.  k_hc_parent
+// writes parent[] whole (k_cc_init is not run), and flatten, mark, scan and label then do what they do for
+// components: none of them needs parent[v] <= v (only cc_join orders by position, and it is not used here), a peak is
+// a root, and roots in ascending position are segments in ascending peak position.  tmp: the components layout.
+//
+// "higher" is a strict total order on the voxels of the graph: by value, equal values (-0 == +0) by the SMALLER
+// position.  every comparison is false for NaN; a voxel with a NaN value is out of the graph, so no NaN gets here
+// as v, and one that gets here as u is no candidate
+__device__ __forceinline__ bool hc_higher(double value_u, uint32_t u, double value_v, uint32_t v)
+{
+    return value_u > value_v || (value_u == value_v && u < v);
+}
+
+// parent: one lane per voxel, the lists' walk from the voxel's own centre as k_db_border runs it, the lane's own value
+// and class plus three registers for the best candidate.  a hit u is a candidate iff it has v's class, a value that
+// is no NaN and hc_higher(u, v).  NO CYCLE CAN FORM: a link goes from v to a voxel strictly above it in a strict total
+// order (hc_higher(v, v) is false, so the walk's own hit at d2 = 0 needs no special case), and a chain of links
+// strictly ascends in it.  cc_root in k_cc_flatten follows these links with no other exit than a root: a cycle would
+// be an endless loop there, so this predicate is the one place where nothing may be loosened.
+// among the candidates: !NEAREST (steepest ascent) keeps the largest value, among equal values the smaller d2, among
+// equal d2 the smaller position; NEAREST (quick shift) keeps the smallest d2, among equal d2 the larger value, then
+// the smaller position.  the walk is in ascending position, so "strictly better replaces" is that last tiebreak.
+// every word written is the lane's own: parent[v] = the link, v itself at a peak, CC_NONE outside the graph and in
+// the pad of the scratch; keep[], size[] and d_count[1] are zeroed as k_cc_init zeroes them
+template <bool NEAREST>
+__global__ __launch_bounds__(256) void k_hc_parent(const int64_t* __restrict__ addr,
+                                                   const uint32_t* __restrict__ index_header, uint32_t room,
+                                                   const uint32_t* __restrict__ leaf,
+                                                   const uint32_t* __restrict__ rank, LatticeDev L, double r2,
+                                                   int32_t dmin, int32_t W, const int64_t* __restrict__ cls,
+                                                   const double* __restrict__ value, uint32_t* __restrict__ parent,
+                                                   uint32_t* __restrict__ keep, int64_t* __restrict__ size,
+                                                   int64_t* __restrict__ link, int64_t* __restrict__ d_count)
+{
+    const uint32_t m = cc_voxels(index_header, room);
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;       // (room <= 2^31)
+    if (v >= room) return;
+    keep[v] = 0u;
+    size[v] = 0;
+    if (v == 0) d_count[1] = 0;
+    uint32_t up = CC_NONE;
+    if (v < m) {
+        const int64_t c = cls ? cls[v] : 0;
+        const double own = value[v];
+        if (c >= 0 && own == own) {
+            int32_t ox, oy, oz;
+            db_cell(addr[v], L, &ox, &oy, &oz);
+            uint32_t best = CC_NONE;
+            double best_value = 0.0, best_d2 = 0.0;
+            nbr_walk_d2(nm_centre(ox, L.min_x, L.edge, L.half_edge), nm_centre(oy, L.min_y, L.edge, L.half_edge),
+                        nm_centre(oz, L.min_z, L.edge, L.half_edge), leaf, rank, L, r2, dmin, W,
+                        [&](uint32_t u, double d2) {
+                            const double x = value[u];
+                            if (!hc_higher(x, u, own, v)) return;        // (NaN too)
+                            if (cls && cls[u] != c) return;
+                            const bool better =
+                                best == CC_NONE ||
+                                (NEAREST ? (d2 < best_d2 || (d2 == best_d2 && x > best_value))
+                                         : (x > best_value || (x == best_value && d2 < best_d2)));
+                            if (better) {
+                                best = u;
+                                best_value = x;
+                                best_d2 = d2;
+                            }
+                        });
+            up = best != CC_NONE ? best : v;
+        }
+        if (link) link[v] = up != CC_NONE ? (int64_t)up : -1;
+    }
+    parent[v] = up;
+}
+
+// peaks, behind the scan: the kept root r writes its position at its segment's number.  roots are numbered in
+// ascending position, so peak[] comes out ascending.  nothing is written where the scratch has no room for the index
+__global__ __launch_bounds__(256) void k_hc_peaks(const uint32_t* __restrict__ index_header, uint32_t room,
+                                                  const uint32_t* __restrict__ parent,
+                                                  const int64_t* __restrict__ size, int64_t min_size,
+                                                  const uint32_t* __restrict__ id, int64_t* __restrict__ peak)
+{
+    const uint32_t m = cc_voxels(index_header, room);
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= m) return;
+    if (parent[v] == v && size[v] >= min_size) peak[id[v]] = (int64_t)v;
+}
+
 // argument checks shared by the entry points that take a built workspace
 int nbr_check_index(nm_ctx* ctx, const char* who, const nm_lattice* lat, const void* d_work, size_t work_bytes,
                     LatticeDev* L, NbrPlan* P)
@@ -1938,6 +2025,74 @@ extern "C" int nm_neighbor_index_regions(nm_ctx* ctx, const nm_lattice* lat, dou
     k_nbr_scan_apply<<<C.scan_blocks, NBR_SCAN_THREADS, 0, s>>>(keep, C.tiles_per_block, C.room, partial, header,
                                                                 d_count);
     k_cc_label<<<blocks, 256, 0, s>>>(index_header, room, parent, size, min_size, keep, d_label, d_size, d_count);
+    NM_HIP(ctx, hipGetLastError());
+    return NM_OK;
+}
+
+// ---- peak-seeking segments of the voxel graph (additive within ABI 7) -------------------------------------------------
+
+extern "C" size_t nm_neighbor_index_hill_climb_workspace_bytes(int64_t n_voxels)
+{
+    if (n_voxels < 0 || n_voxels >= (int64_t)1 << 31) return 0;
+    return cc_plan(n_voxels).bytes;
+}
+
+extern "C" int nm_neighbor_index_hill_climb(nm_ctx* ctx, const nm_lattice* lat, double radius, int32_t mode,
+                                            const void* d_work, size_t work_bytes, const double* d_value,
+                                            const int64_t* d_class, const int64_t* d_weight, int64_t min_size,
+                                            int64_t* d_label, int64_t* d_size, int64_t* d_peak, int64_t* d_link,
+                                            int64_t* d_count, void* d_tmp, size_t tmp_bytes, void* stream)
+{
+    NM_ENTER_STREAM(ctx, stream);
+    if (!d_value || !d_label || !d_size || !d_peak || !d_count)
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_hill_climb: bad arguments");
+    if (mode != NM_CLIMB_HIGHEST && mode != NM_CLIMB_NEAREST)
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_hill_climb: mode = %d is neither NM_CLIMB_HIGHEST nor "
+                "NM_CLIMB_NEAREST", mode);
+    if (!(radius >= 0.0))      // (NaN fails)
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_hill_climb: radius must be >= 0");
+    LatticeDev L;
+    NbrPlan P;
+    int rc = nbr_check_index(ctx, "nm_neighbor_index_hill_climb", lat, d_work, work_bytes, &L, &P);
+    if (rc) return rc;
+    int32_t dmin = 0;
+    const int W = nbr_candidate_width(radius, lat->edge, &dmin);
+    if (W < 0) NM_FAIL(ctx, NM_ERR_RADIUS, "radius/edge ratio outside the supported range");
+    if (!d_tmp || tmp_bytes < cc_plan(0).bytes)
+        NM_FAIL(ctx, NM_ERR_WORKSPACE, "nm_neighbor_index_hill_climb: temporary workspace too small");
+    const CcPlan C = cc_plan_of(tmp_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    const char* w = (const char*)d_work;
+    const uint32_t* index_header = (const uint32_t*)w;
+    const uint32_t* leaf = (const uint32_t*)(w + P.off_leaf);
+    const uint32_t* rank = (const uint32_t*)(w + P.off_rank);
+    char* t = (char*)d_tmp;
+    uint32_t* header = (uint32_t*)t;
+    uint32_t* partial = (uint32_t*)(t + C.off_partial);
+    int64_t* addr = (int64_t*)(t + C.off_addr);
+    int64_t* size = (int64_t*)(t + C.off_size);
+    uint32_t* parent = (uint32_t*)(t + C.off_parent);
+    uint32_t* keep = (uint32_t*)(t + C.off_keep);
+    const uint32_t room = (uint32_t)C.room;
+    const unsigned blocks = (unsigned)(C.room / 256);
+    const uint64_t words = P.superblocks * NM_LEAF_WORDS;
+    const double r2 = radius * radius;
+    k_nbr_addresses<<<(unsigned)((words + 255) / 256), 256, 0, s>>>(leaf, rank, index_header, L, words, addr, room);
+    // the forest: every voxel's uphill link (in the place of k_cc_init and k_cc_link)
+    if (mode == NM_CLIMB_NEAREST)
+        k_hc_parent<true><<<blocks, 256, 0, s>>>(addr, index_header, room, leaf, rank, L, r2, dmin, W, d_class,
+                                                 d_value, parent, keep, size, d_link, d_count);
+    else
+        k_hc_parent<false><<<blocks, 256, 0, s>>>(addr, index_header, room, leaf, rank, L, r2, dmin, W, d_class,
+                                                  d_value, parent, keep, size, d_link, d_count);
+    k_cc_flatten<<<(unsigned)(C.room / CC_FLAT_THREADS), CC_FLAT_THREADS, 0, s>>>(index_header, room, d_weight,
+                                                                                  parent, size);
+    k_cc_mark<<<blocks, 256, 0, s>>>(index_header, room, parent, size, min_size, keep, d_count);
+    k_nbr_scan_reduce<<<C.scan_blocks, NBR_SCAN_THREADS, 0, s>>>(keep, C.tiles_per_block, C.room, partial);
+    k_nbr_scan_apply<<<C.scan_blocks, NBR_SCAN_THREADS, 0, s>>>(keep, C.tiles_per_block, C.room, partial, header,
+                                                                d_count);
+    k_cc_label<<<blocks, 256, 0, s>>>(index_header, room, parent, size, min_size, keep, d_label, d_size, d_count);
+    k_hc_peaks<<<blocks, 256, 0, s>>>(index_header, room, parent, size, min_size, keep, d_peak);
     NM_HIP(ctx, hipGetLastError());
     return NM_OK;
 }

@@ -303,6 +303,9 @@ class NeighborIndex(object):
         .regions(radius, voxel_normal=None, max_angle=None, voxel_value=None, max_step=None, voxel_seed=None, ...)
                                 -> (labels (M,), sizes (C,), seed (M,)): region growing - components of the seed
                                 voxels under the edges whose normals / values agree, the other voxels attached
+        .hill_climb(radius, voxel_value, link="highest", ...) -> (labels (M,), sizes (C,), peaks (C,)): every voxel
+                                steps to a higher neighbor, a segment is what climbs to the same peak - it separates
+                                objects that touch, which the three connectivity rules above weld into one
         .component_table(labels, voxel_weight=None) -> (C, 25): one row of descriptors per component (segment_table
                                 over voxels())
     torch in, torch out; numpy in, numpy out (addresses / voxels / point_counts / members / components / dbscan follow the
@@ -781,6 +784,76 @@ class NeighborIndex(object):
         out = self._regions_device(radius, normal, min_cos, value, steps, seed, cls, weight, int(min_size))
         return out if self._as_torch else tuple(t.cpu().numpy() for t in out)
 
+    def _hill_climb_device(self, radius, value, mode, voxel_class, voxel_weight, min_size, want_link):
+        """enqueue nm_neighbor_index_hill_climb on device tensors - value fp64 (M,) contiguous, class and weight int64
+        (M,) or None, mode NM_CLIMB_* - (labels, sizes, peaks, link or None); one host read, of the counts"""
+        rt = self._rt
+        m = self.n_voxels
+        labels = torch.empty(m, dtype=torch.int64, device=rt.device)
+        sizes = torch.empty(max(m, 1), dtype=torch.int64, device=rt.device)
+        peaks = torch.empty(max(m, 1), dtype=torch.int64, device=rt.device)
+        link = torch.empty(m, dtype=torch.int64, device=rt.device) if want_link else None
+        if m == 0:
+            return labels, sizes[:0], peaks[:0], link
+        count = torch.empty(2, dtype=torch.int64, device=rt.device)
+        nbytes = int(rt.lib.nm_neighbor_index_hill_climb_workspace_bytes(m))
+        tmp = rt.workspace(nbytes)
+        rt.check(rt.lib.nm_neighbor_index_hill_climb(
+            rt.ctx, ctypes.byref(self.filter.nm_lattice), radius, mode, _device.ptr(self._work), self._work.numel(),
+            _device.ptr(value), _device.ptr(voxel_class), _device.ptr(voxel_weight), min_size, _device.ptr(labels),
+            _device.ptr(sizes), _device.ptr(peaks), _device.ptr(link), _device.ptr(count), _device.ptr(tmp), nbytes,
+            rt.stream()))
+        kept = int(count[0])
+        if kept < 0:        # (cannot happen: the scratch was sized for this handle's M)
+            raise _ffi.NimrudHipError("nm_neighbor_index_hill_climb: scratch too small for the index")
+        return labels, sizes[:kept], peaks[:kept], link
+
+    def hill_climb(self, radius, voxel_value, link="highest", voxel_class=None, voxel_weight=None, min_size=1,
+                   return_link=False):
+        """(labels int64 (M,), sizes int64 (C,), peaks int64 (C,)) and, with return_link, link int64 (M,): peak-seeking
+        segments of the voxel graph of components() - voxels u and v are neighbors when lists(voxels(), radius) names
+        one for the other and both carry the same voxel_class >= 0 (None: one class for all).  voxel_value (floating
+        point, (M,)) is the height every voxel climbs on; a voxel with a NaN value or a negative class is out of the
+        graph: label -1, link -1.  u is HIGHER than v when value[u] > value[v], or the values are equal and u < v (the
+        smaller position) - a strict total order, so links never form a cycle.  every voxel of the graph links to one of
+        its higher neighbors of its class:
+          link="highest" (steepest ascent, crown delineation with height as the value): the largest value; among equal
+            values the smaller squared distance as lists() forms it; among equal distances the smaller position.
+          link="nearest" (quick shift, e.g. on dbscan(return_density=True)'s density): the smallest squared distance;
+            among equal distances the larger value; then the smaller position.
+        a voxel without a higher neighbor is a PEAK and links to itself; a segment is everything whose links lead to
+        the same peak, so two objects that touch stay two where components(), dbscan() and regions() weld them.  a
+        plateau of equal values climbs to its smallest position as far as the radius lets it (one that is not convex
+        at that radius may split).  a segment's size is the sum of voxel_weight (integers, (M,); None counts voxels)
+        over its members; segments below min_size are dropped, their members get -1.  kept segments are numbered
+        0..C-1 in ascending order of their peak's position, peaks[c] is that position (voxels()[peaks] are the peaks'
+        centres).  link is every voxel's uphill neighbor, whatever min_size dropped.  the result is a function of
+        the arguments alone, the same bit for bit on every run."""
+        self._need_index("hill_climb")
+        radius = float(radius)
+        if not radius >= 0.0:
+            raise ValueError("radius must be a number >= 0")
+        if isinstance(min_size, bool) or not isinstance(min_size, (int, np.integer)):
+            raise ValueError("min_size must be an integer")
+        if link not in _ffi.NM_CLIMB:
+            raise ValueError("link must be 'highest' or 'nearest'")
+        value = self._voxel_heights(voxel_value, "voxel_value")
+        cls = None if voxel_class is None else self._voxel_integers(voxel_class, "voxel_class")
+        weight = None if voxel_weight is None else self._voxel_integers(voxel_weight, "voxel_weight")
+        out = self._hill_climb_device(radius, value, _ffi.NM_CLIMB[link], cls, weight, int(min_size),
+                                      bool(return_link))
+        out = out if return_link else out[:3]
+        return out if self._as_torch else tuple(t.cpu().numpy() for t in out)
+
+    def _voxel_heights(self, values, what):
+        """a floating-point array with one entry per voxel as a contiguous fp64 device tensor (M,)"""
+        t = torch.as_tensor(values)
+        if not t.dtype.is_floating_point:
+            raise ValueError("%s must have a floating-point dtype" % what)
+        if t.ndim != 1 or t.shape[0] != self.n_voxels:
+            raise ValueError("%s must have one entry per voxel" % what)
+        return t.to(device=self._rt.device, dtype=torch.float64).contiguous()
+
     def component_table(self, labels, voxel_weight=None):
         """fp64 (C, 25): segment_table over voxels() for the labels components() returned - one row of descriptors
         per component of the voxel graph (columns: SEGMENT_COLUMNS).  voxels with label -1 are in no segment.
@@ -972,6 +1045,54 @@ def smooth_regions(cloud, edge_length, radius, max_angle, normal_radius=None, ma
     if isinstance(cloud, torch.Tensor):
         return point_labels, sizes, table
     return point_labels.cpu().numpy(), sizes.cpu().numpy(), table.cpu().numpy()
+
+
+def peak_segments(cloud, edge_length, radius, point_value=None, link="highest", point_class=None, min_points=1):
+    """(point_labels int64 (N,), sizes int64 (C,), peak_xyz fp64 (C, 3), peak_value fp64 (C,)): the peak-seeking
+    segments of a cloud in one call - individual tree crowns with the height as the value, the modes of a density.
+    the cloud is voxel-filtered at `edge_length`; a voxel's value is the MAXIMUM of point_value (floating point, (N,);
+    None: the z column) over its points; NeighborIndex.hill_climb lets every voxel step to a higher voxel within
+    `radius` (link "highest" or "nearest", see there) and a segment is what climbs to the same peak.  every point
+    takes the label of its voxel.  sizes and min_points count POINTS (the voxels are weighted by point_counts()):
+    segments of fewer points are dropped, their points get -1.  segments are numbered 0..C-1 in ascending order of
+    their peak's voxel position; peak_xyz are the centres of the peak voxels, peak_value their values.
+    point_class as in cluster_cloud: a voxel's class is the MINIMUM class of the points in it, links stay within a
+    class, a negative class is out.  NaN point values are not supported (as in voxel_table).
+    one NeighborIndex (method "index"), built and asked once.  torch in, torch out; numpy in, numpy out."""
+    index = NeighborIndex(cloud, edge_length, method="index")
+    rt = index._rt
+    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)):
+        raise ValueError("min_points must be an integer")
+    radius = float(radius)
+    if not radius >= 0.0:
+        raise ValueError("radius must be a number >= 0")
+    if link not in _ffi.NM_CLIMB:
+        raise ValueError("link must be 'highest' or 'nearest'")
+    n = index._search.shape[0]
+    if point_value is None:
+        column = index._search[:, 2]
+    else:
+        column = torch.as_tensor(point_value)
+        if not column.dtype.is_floating_point:
+            raise ValueError("point_value must have a floating-point dtype")
+        if column.ndim != 1 or column.shape[0] != n:
+            raise ValueError("point_value must have one entry per point")
+        column = column.to(device=rt.device, dtype=torch.float64)
+    value = index.voxel_table(column, reduce="max")[:, 0].contiguous()
+    voxel_class = None
+    if point_class is not None:
+        classes = _integer_column(point_class, n, rt.device, "point_class", "point")
+        # min of an integer-valued fp64 column: exact
+        voxel_class = index.voxel_table(classes.to(torch.float64), reduce="min")[:, 0].to(torch.int64)
+    weight = index._grouping()[0]
+    labels, sizes, peaks, _ = index._hill_climb_device(radius, value, _ffi.NM_CLIMB[link], voxel_class, weight,
+                                                       int(min_points), False)
+    voxel = index._voxel_of_device(index._search)
+    point_labels = torch.where(voxel >= 0, labels[voxel.clamp(min=0)], torch.full_like(voxel, -1))
+    peak_xyz = index.filter.address_to_coordinate(index._addresses_device())[peaks]
+    peak_value = value[peaks]
+    out = (point_labels, sizes, peak_xyz, peak_value)
+    return out if isinstance(cloud, torch.Tensor) else tuple(t.cpu().numpy() for t in out)
 
 
 # columns of a segment table (nm_segment_table): name -> slice
