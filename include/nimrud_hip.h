@@ -511,6 +511,65 @@ int nm_neighbor_index_hill_climb(nm_ctx* ctx, const nm_lattice* lat, double radi
                                  int64_t* d_label, int64_t* d_size, int64_t* d_peak, int64_t* d_link,
                                  int64_t* d_count, void* d_tmp, size_t tmp_bytes, void* stream);
 
+/* ---- the adjacency of a labelling of the voxel graph (new symbols only: additive within ABI 7) -------------------
+ * which segments touch, over how many voxel edges, and how high the pass between them lies: the region adjacency
+ * graph of any labelling of the voxels, taken off the index.  no list of the voxel graph is written.
+ *   graph: as nm_neighbor_index_components - voxels u != v are neighbors iff ((dx*dx + dy*dy) + dz*dz) <= r*r on
+ *     their centres (inclusive, unfused) and both carry the same class >= 0 (d_class NULL = class 0 for all); with
+ *     d_value (fp64[M], may be NULL) a voxel whose value is NaN is out of the graph.
+ *   d_label (int64[M]): a negative label is "in no segment"; labels >= 2^31 are not valid (two labels are packed into
+ *     a 64-bit key): such voxels are left out and counted in d_count[1].
+ *   an edge {u, v} of the graph CROSSES when label[u] and label[v] are both >= 0 and differ.  the result has one row
+ *     per unordered pair of labels a < b that at least one crossing edge joins: links = the number of such edges
+ *     (every undirected edge once), saddle = the largest min(value[u], value[v]) over them.
+ *   three calls, the host reads one count between them (the number of crossing edges is not known before the walk):
+ *   1. nm_neighbor_index_adjacency with d_key NULL: every voxel walks the forward half of its window and counts its
+ *      records; d_count (int64[2]) = {R = records, labels >= 2^31}; d_count[1] = -1 where d_tmp has no room for the
+ *      index's M.  a record is a run of consecutive crossing edges of one voxel towards one label: R <= the number
+ *      of crossing edges.
+ *   2. the same call, same arguments and the same d_tmp untouched, with d_key (int64[capacity]), d_links
+ *      (int64[capacity]) and, iff d_value is given, d_saddle (fp64[capacity]), capacity >= R: record i is
+ *      key[i] = (a << 32) | b, links[i], saddle[i].  with capacity < R nothing is written and d_count[0] = -1.
+ *   3. the caller orders the keys (any sort of 64-bit integers; the order among equal keys does not matter) and
+ *      nm_neighbor_index_adjacency_reduce takes the sorted keys, d_order (int64[R], may be NULL = identity: record
+ *      d_order[i] has the key d_key[i]) and the records' links and saddles: d_pair (int64[R][2]), d_links, d_saddle
+ *      (room for R entries each, not overlapping the inputs) get one row per run of equal keys, ascending by (a, b);
+ *      d_count[0] = E, the rows.  links add up and saddles take the maximum on integers (the saddle through its
+ *      order-preserving integer image): the same bit for bit in any order and on every run; -0 and +0 are one number,
+ *      of which +0 is written.
+ *   d_tmp: nm_neighbor_index_adjacency_workspace_bytes(M, R) bytes serve any of the three calls (M, 0) serves the
+ *     first two; the query needs no GPU, is monotone and 0 for counts < 0 or >= 2^31.
+ *   errors, all before anything is queued: NM_ERR_INVALID for null d_label / d_count, a NaN or negative radius, record
+ *     pointers that do not go together; NM_ERR_RADIUS as nm_neighbor_index_lists, and where room * W^3 / 2 (the most
+ *     records the 32-bit scan could have to count) reaches 2^32; NM_ERR_WORKSPACE, NM_ERR_LATTICE as everywhere. */
+size_t nm_neighbor_index_adjacency_workspace_bytes(int64_t n_voxels, int64_t n_records);
+int nm_neighbor_index_adjacency(nm_ctx* ctx, const nm_lattice* lat, double radius, const void* d_work,
+                                size_t work_bytes, const int64_t* d_label, const double* d_value,
+                                const int64_t* d_class, int64_t capacity, int64_t* d_key, int64_t* d_links,
+                                double* d_saddle, int64_t* d_count, void* d_tmp, size_t tmp_bytes, void* stream);
+int nm_neighbor_index_adjacency_reduce(nm_ctx* ctx, int64_t n_records, const int64_t* d_key, const int64_t* d_order,
+                                       const int64_t* d_links_in, const double* d_saddle_in, int64_t* d_pair,
+                                       int64_t* d_links, double* d_saddle, int64_t* d_count, void* d_tmp,
+                                       size_t tmp_bytes, void* stream);
+
+/* merging peaks by prominence (topological persistence) on the rows of the adjacency: HOST code, host pointers, no
+ * context and no GPU call - it runs on a machine without a GPU.
+ *   n_segments S, peak_value[S] (no NaN); n_rows E, pair[E][2] with 0 <= a < b < S, saddle[E] (no NaN);
+ *   min_prominence >= 0, may be +inf.  segment a is HIGHER than b iff peak_value[a] > peak_value[b], or they are
+ *   equal and a < b.
+ *   the rows are taken by descending saddle, equal saddles by ascending (a, b), through a union-find in which every
+ *   segment starts as its own root: ra = find(a), rb = find(b), nothing to do where they are equal; lo the lower of
+ *   the two roots, hi the higher; if peak_value[lo] - saddle < min_prominence (fp64, strict) lo is merged under hi
+ *   and hi stays the root; otherwise nothing is merged, and if lo has no recorded prominence yet,
+ *   prominence[lo] = peak_value[lo] - saddle.
+ *   output: root[S], the surviving root of every segment; prominence[S]: of a root what was recorded, +inf if it
+ *   never lost; of a merged segment the difference it was merged at.  scratch: E + S int64.
+ *   NM_ERR_INVALID for negative counts, null pointers, a NaN or negative min_prominence, a NaN value or saddle, a row
+ *   that is no pair a < b of segments; nothing else can fail. */
+int nm_merge_by_prominence(int64_t n_segments, const double* peak_value, int64_t n_rows, const int64_t* pair,
+                           const double* saddle, double min_prominence, int64_t* scratch, int64_t* root,
+                           double* prominence);
+
 /* ---- per-segment descriptors of a labelled cloud (new symbols only: additive within ABI 7) --------------------
  * what a cluster is as an object: how many points, where, its box, its shape and which way it points.  the last
  * stage behind a classifier and nm_neighbor_index_components; the table is a plain fp64 feature matrix.

@@ -5,6 +5,9 @@
 
 #include "nm_common.h"
 
+#include <algorithm>
+#include <cmath>
+
 extern "C" int nm_abi_version(void) { return 7; }
 
 // nm_create has no context to leave a message in yet: what failed goes to stderr
@@ -751,5 +754,72 @@ extern "C" int nm_descriptors(nm_ctx* ctx, const double* d_feat, int64_t n, int3
     k_descriptors<<<(int)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(
         d_feat, n, n_scales, feat_stride, d_out, out_stride);
     NM_HIP(ctx, hipGetLastError());
+    return NM_OK;
+}
+
+// ---- merging peaks by prominence: host code, no GPU call, no context (additive within ABI 7) -------------------------
+// topological persistence on the segment graph of nm_neighbor_index_adjacency: S segments and E rows are small next
+// to the voxel graph, and the merge is sequential - one ordering of the rows and a union-find over the segments.
+// root[] is the union-find's parent array while the rows are taken (the HIGHER root stays the root, so a tree's root
+// is its highest peak), and every segment's root in the end.  the paths are halved as they are walked
+static inline bool nm_peak_higher(const double* p, int64_t a, int64_t b)
+{
+    return p[a] > p[b] || (p[a] == p[b] && a < b);
+}
+
+static inline int64_t nm_peak_find(int64_t* root, int64_t x)
+{
+    while (root[x] != x) {
+        root[x] = root[root[x]];
+        x = root[x];
+    }
+    return x;
+}
+
+extern "C" int nm_merge_by_prominence(int64_t n_segments, const double* peak_value, int64_t n_rows,
+                                      const int64_t* pair, const double* saddle, double min_prominence,
+                                      int64_t* scratch, int64_t* root, double* prominence)
+{
+    const int64_t S = n_segments, E = n_rows;
+    if (S < 0 || E < 0 || !(min_prominence >= 0.0)) return NM_ERR_INVALID;      // (NaN fails)
+    if ((S > 0 && (!peak_value || !root || !prominence)) || (E > 0 && (!pair || !saddle)) ||
+        (S + E > 0 && !scratch))
+        return NM_ERR_INVALID;
+    for (int64_t c = 0; c < S; ++c)
+        if (peak_value[c] != peak_value[c]) return NM_ERR_INVALID;
+    for (int64_t e = 0; e < E; ++e) {
+        const int64_t a = pair[2 * e], b = pair[2 * e + 1];
+        if (a < 0 || b <= a || b >= S || saddle[e] != saddle[e]) return NM_ERR_INVALID;
+    }
+    int64_t* order = scratch;            // E entries: the rows by descending saddle, equal saddles by (a, b)
+    int64_t* recorded = scratch + E;     // S entries: has this root's prominence been recorded?
+    for (int64_t e = 0; e < E; ++e) order[e] = e;
+    std::sort(order, order + E, [&](int64_t x, int64_t y) {
+        if (saddle[x] != saddle[y]) return saddle[x] > saddle[y];
+        if (pair[2 * x] != pair[2 * y]) return pair[2 * x] < pair[2 * y];
+        if (pair[2 * x + 1] != pair[2 * y + 1]) return pair[2 * x + 1] < pair[2 * y + 1];
+        return x < y;
+    });
+    for (int64_t c = 0; c < S; ++c) {
+        root[c] = c;
+        recorded[c] = 0;
+        prominence[c] = INFINITY;
+    }
+    for (int64_t k = 0; k < E; ++k) {
+        const int64_t e = order[k];
+        const int64_t ra = nm_peak_find(root, pair[2 * e]), rb = nm_peak_find(root, pair[2 * e + 1]);
+        if (ra == rb) continue;
+        const bool a_higher = nm_peak_higher(peak_value, ra, rb);
+        const int64_t lo = a_higher ? rb : ra, hi = a_higher ? ra : rb;
+        const double rise = peak_value[lo] - saddle[e];
+        if (rise < min_prominence) {
+            root[lo] = hi;
+            prominence[lo] = rise;       // what it had when it was merged
+        } else if (!recorded[lo]) {
+            recorded[lo] = 1;
+            prominence[lo] = rise;
+        }
+    }
+    for (int64_t c = 0; c < S; ++c) root[c] = nm_peak_find(root, c);
     return NM_OK;
 }

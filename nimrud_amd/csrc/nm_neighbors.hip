@@ -9,6 +9,7 @@
 // reductions of per-point columns, and per-neighborhood count / mean / min / max of a voxel table without a list.
 // and the graph itself: the connected components of the voxels under "within r", by a lock-free union-find, and its
 // density-based clusters (DBSCAN): a density walk, the same union-find on the core voxels, a border walk.
+// and the graph of a labelling's segments: which of them touch, over how many edges, at which saddle (adjacency).
 //
 // workspace (nm_neighbor_index_workspace_bytes), S = superblocks of the lattice (at most 2^NM_DENSE_LOG2):
 //   header  256 B      [0] M, written by the scan
@@ -1488,6 +1489,248 @@ __global__ __launch_bounds__(256) void k_hc_peaks(const uint32_t* __restrict__ i
     if (parent[v] == v && size[v] >= min_size) peak[id[v]] = (int64_t)v;
 }
 
+// ---- adjacency: which segments of a labelling touch, over how many edges, and how high the pass between them lies -----
+// the region adjacency graph of a labelling of the voxels, taken off the index: no list of the voxel graph is written.
+// one lane per voxel walks the FORWARD half of its window (nbr_walk_forward), so every undirected edge {v, u} is met
+// exactly once, from its smaller end, in ascending u - nothing has to be kept from counting twice.  an edge CROSSES
+// when both ends carry a label >= 0, the labels differ, the classes agree (and are >= 0) and neither value is NaN.
+// how many crossing edges there are is not known before the walk: the walk runs twice, once to count the records of
+// every voxel (scanned in place, k_nbr_scan_*), once to write them at the voxel's offset; the host reads the total
+// between the two and brings the room.
+//
+// a RECORD is (key, links, saddle): key = (a << 32) | b with a < b the two labels, links a number of edges, saddle the
+// largest min(value[v], value[u]) over them.  consecutive hits of one lane with the SAME label on the other side are one
+// record (hits come in ascending position, and neighbors in a row mostly share a segment): the lane keeps one open
+// record in registers and closes it when the label changes.  both passes run the same walk, so they agree on the
+// number of records.  records are then ordered by key (by the caller: any sort of 64-bit keys) and reduced, one row per
+// run of equal keys: links add up, saddles take the maximum - integer adds and a maximum, the same in any order.
+//
+// tmp of the walk (nm_neighbor_index_adjacency_workspace_bytes), room = the voxel count rounded up to whole scan tiles:
+//   header  256 B      word 0: records (the scan's total)
+//   partial 8 KB       the scan's per-block sums
+//   addr    room * 8   the address of every voxel (k_nbr_addresses)
+//   count   room * 4   records of every voxel, then (scanned in place) where its first one goes
+// tmp of the reduction, rpad = the record count rounded up to whole scan tiles:
+//   header  256 B      word 0: rows (the scan's total)
+//   partial 8 KB
+//   row     rpad * 4   1 at the first record of every run of equal keys, then (scanned in place) rows before it
+struct AdjPlan {
+    int64_t room;
+    int32_t scan_blocks, tiles_per_block;
+    size_t off_partial, off_addr, off_count, bytes;
+};
+
+AdjPlan adj_plan_tiles(int64_t tiles)
+{
+    AdjPlan A;
+    A.room = tiles * NBR_SCAN_TILE;
+    A.scan_blocks = (int32_t)(tiles < NBR_SCAN_MAX_BLOCKS ? tiles : NBR_SCAN_MAX_BLOCKS);
+    A.tiles_per_block = (int32_t)((tiles + A.scan_blocks - 1) / A.scan_blocks);
+    A.off_partial = NBR_HEADER_BYTES;
+    A.off_addr = A.off_partial + (size_t)NBR_SCAN_MAX_BLOCKS * 4;
+    A.off_count = A.off_addr + (size_t)A.room * 8;
+    A.bytes = A.off_count + (size_t)A.room * 4;
+    return A;
+}
+
+AdjPlan adj_plan(int64_t n) { return adj_plan_tiles(n > 0 ? (n + NBR_SCAN_TILE - 1) / NBR_SCAN_TILE : 1); }
+
+// the plan a scratch of `bytes` has room for (at least adj_plan(0).bytes), as cc_plan_of
+AdjPlan adj_plan_of(size_t bytes)
+{
+    const size_t fixed = adj_plan(0).bytes - (size_t)NBR_SCAN_TILE * 12;
+    int64_t tiles = (int64_t)((bytes - fixed) / ((size_t)NBR_SCAN_TILE * 12));
+    const int64_t most = ((int64_t)1 << 31) / NBR_SCAN_TILE;
+    return adj_plan_tiles(tiles < most ? tiles : most);
+}
+
+struct AdjRows {
+    int64_t rpad;
+    int32_t scan_blocks, tiles_per_block;
+    size_t off_partial, off_row, bytes;
+};
+
+AdjRows adj_rows(int64_t n)
+{
+    const int64_t tiles = n > 0 ? (n + NBR_SCAN_TILE - 1) / NBR_SCAN_TILE : 1;
+    AdjRows R;
+    R.rpad = tiles * NBR_SCAN_TILE;
+    R.scan_blocks = (int32_t)(tiles < NBR_SCAN_MAX_BLOCKS ? tiles : NBR_SCAN_MAX_BLOCKS);
+    R.tiles_per_block = (int32_t)((tiles + R.scan_blocks - 1) / R.scan_blocks);
+    R.off_partial = NBR_HEADER_BYTES;
+    R.off_row = R.off_partial + (size_t)NBR_SCAN_MAX_BLOCKS * 4;
+    R.bytes = R.off_row + (size_t)R.rpad * 4;
+    return R;
+}
+
+constexpr int64_t ADJ_LABEL_LIMIT = (int64_t)1 << 31;       // labels are packed two to a 64-bit key
+
+// the order-preserving integer image of an fp64 that is no NaN: x < y iff image(x) < image(y), -0 just below +0.
+// no such number has the image 0 (that would be a NaN with every bit set), so 0 is "nothing yet" under a maximum
+__device__ __forceinline__ unsigned long long adj_image(double x)
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+__device__ __forceinline__ double adj_number(unsigned long long image)
+{
+    const unsigned long long b = (image >> 63) ? (image & 0x7FFFFFFFFFFFFFFFull) : ~image;
+    return __longlong_as_double((long long)b);
+}
+
+// the walk, both passes.  !EMIT: count[v] = the records of voxel v (0 outside the graph and in the pad of the scratch),
+// d_count[1] += the labels that are no valid label (>= 2^31; the host has zeroed it), -1 there where the scratch has no
+// room for the index.  EMIT: count[] holds the scanned offsets and header[0] the total; the lane writes its records
+// from its offset on, every word its own - or nothing at all, and d_count[0] = -1, where the total exceeds `capacity`
+template <bool EMIT>
+__global__ __launch_bounds__(256) void k_adj_walk(const int64_t* __restrict__ addr,
+                                                  const uint32_t* __restrict__ index_header, uint32_t room,
+                                                  const uint32_t* __restrict__ leaf,
+                                                  const uint32_t* __restrict__ rank, LatticeDev L, double r2,
+                                                  int32_t dmin, int32_t W, const int64_t* __restrict__ label,
+                                                  const int64_t* __restrict__ cls,
+                                                  const double* __restrict__ value, uint32_t* __restrict__ count,
+                                                  const uint32_t* __restrict__ header, int64_t capacity,
+                                                  int64_t* __restrict__ key, int64_t* __restrict__ links,
+                                                  double* __restrict__ saddle, int64_t* __restrict__ d_count)
+{
+    const uint32_t m = cc_voxels(index_header, room);
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;       // (room <= 2^31)
+    if (v >= room) return;
+    if (EMIT) {
+        if ((int64_t)header[0] > capacity) {
+            if (v == 0) d_count[0] = -1;
+            return;
+        }
+    } else if (v == 0 && index_header[0] > room) {
+        d_count[1] = -1;          // (m is 0 then: nobody adds to this word)
+    }
+    uint32_t n = 0;
+    bool bad = false;
+    if (v < m) {
+        const int64_t la = label[v];
+        const int64_t c = cls ? cls[v] : 0;
+        const double own = value ? value[v] : 0.0;
+        bad = la >= ADJ_LABEL_LIMIT;
+        if (la >= 0 && !bad && c >= 0 && own == own) {
+            int32_t ox, oy, oz;
+            db_cell(addr[v], L, &ox, &oy, &oz);
+            const int64_t at = EMIT ? (int64_t)count[v] : 0;
+            int64_t open = -1;          // the label on the other side of the open record; none yet
+            int64_t open_links = 0;
+            double open_saddle = 0.0;
+            auto close = [&]() {
+                if (open < 0) return;
+                if (EMIT) {
+                    const int64_t lo = la < open ? la : open, hi = la < open ? open : la;
+                    if (at + n < capacity) {        // (always, for the labels, classes and values the count saw)
+                        key[at + n] = (lo << 32) | hi;
+                        links[at + n] = open_links;
+                        if (saddle) saddle[at + n] = open_saddle;
+                    }
+                }
+                ++n;
+            };
+            nbr_walk_forward(ox, oy, oz, leaf, rank, L, r2, dmin, W, [&](uint32_t u) {
+                const int64_t lb = label[u];
+                if (lb < 0 || lb == la || lb >= ADJ_LABEL_LIMIT) return;
+                if (cls && cls[u] != c) return;
+                const double x = value ? value[u] : 0.0;
+                if (x != x) return;
+                const double pass = x < own ? x : own;
+                if (lb == open) {
+                    ++open_links;
+                    if (pass > open_saddle) open_saddle = pass;
+                } else {
+                    close();
+                    open = lb;
+                    open_links = 1;
+                    open_saddle = pass;
+                }
+            });
+            close();
+        }
+    }
+    if (!EMIT) {
+        count[v] = n;
+        const unsigned long long bads = __ballot(bad);
+        if (bads && (threadIdx.x & 63) == 0)
+            atomicAdd((unsigned long long*)(d_count + 1), (unsigned long long)__popcll(bads));
+    }
+}
+
+// reduction, before the scan: 1 at the first record of every run of equal keys (the keys are sorted), 0 in the pad;
+// the rows' sums and maxima start from nothing
+__global__ __launch_bounds__(256) void k_adj_heads(const int64_t* __restrict__ key, int64_t n, int64_t rpad,
+                                                   uint32_t* __restrict__ row, int64_t* __restrict__ links,
+                                                   unsigned long long* __restrict__ image)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rpad) return;
+    row[i] = (i < n && (i == 0 || key[i] != key[i - 1])) ? 1u : 0u;
+    if (i < n) {
+        links[i] = 0;
+        if (image) image[i] = 0ull;
+    }
+}
+
+// reduction, behind the scan: record i belongs to row  row[i] + head(i) - 1.  the lanes of a wave hold consecutive
+// records, so the records of one row are consecutive lanes: a segmented scan over the wave adds them up, and the last
+// lane of every row in the wave hands the wave's part to the row - one atomic add and one atomic maximum per row and
+// wave, on integers: the same result whatever the order.  the first record of a row writes its pair
+__global__ __launch_bounds__(256) void k_adj_reduce(const int64_t* __restrict__ key,
+                                                    const int64_t* __restrict__ order,
+                                                    const int64_t* __restrict__ links_in,
+                                                    const double* __restrict__ saddle_in, int64_t n,
+                                                    const uint32_t* __restrict__ row, int64_t* __restrict__ pair,
+                                                    int64_t* __restrict__ links,
+                                                    unsigned long long* __restrict__ image)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    uint32_t r = CC_NONE;
+    unsigned long long sum = 0ull, top = 0ull;
+    if (i < n) {
+        const int64_t k = key[i];
+        const bool head = i == 0 || k != key[i - 1];
+        r = row[i] + (head ? 1u : 0u) - 1u;
+        const int64_t from = order ? order[i] : i;
+        sum = (unsigned long long)links_in[from];
+        if (saddle_in) top = adj_image(saddle_in[from]);
+        if (head) {
+            pair[2 * (int64_t)r] = k >> 32;
+            pair[2 * (int64_t)r + 1] = k & 0xFFFFFFFFll;
+        }
+    }
+    // (no lane has left: the shuffles below see all 64)
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t r_below = __shfl_up(r, off);
+        const unsigned long long sum_below = __shfl_up(sum, off);
+        const unsigned long long top_below = __shfl_up(top, off);
+        if (lane >= off && r_below == r) {
+            sum += sum_below;
+            top = top_below > top ? top_below : top;
+        }
+    }
+    const uint32_t r_above = __shfl_down(r, 1);
+    if (r != CC_NONE && (lane == 63 || r_above != r)) {
+        atomicAdd((unsigned long long*)&links[r], sum);
+        if (image) atomicMax(&image[r], top);
+    }
+}
+
+// the maxima back from their integer image to numbers, in place
+__global__ __launch_bounds__(256) void k_adj_saddles(const uint32_t* __restrict__ header,
+                                                     unsigned long long* __restrict__ image)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (int64_t)header[0]) return;
+    const double x = adj_number(image[e]);
+    ((double*)image)[e] = x;
+}
+
 // argument checks shared by the entry points that take a built workspace
 int nbr_check_index(nm_ctx* ctx, const char* who, const nm_lattice* lat, const void* d_work, size_t work_bytes,
                     LatticeDev* L, NbrPlan* P)
@@ -2093,6 +2336,112 @@ extern "C" int nm_neighbor_index_hill_climb(nm_ctx* ctx, const nm_lattice* lat, 
                                                                 d_count);
     k_cc_label<<<blocks, 256, 0, s>>>(index_header, room, parent, size, min_size, keep, d_label, d_size, d_count);
     k_hc_peaks<<<blocks, 256, 0, s>>>(index_header, room, parent, size, min_size, keep, d_peak);
+    NM_HIP(ctx, hipGetLastError());
+    return NM_OK;
+}
+
+// ---- the adjacency of a labelling of the voxel graph (additive within ABI 7) -------------------------------------------
+
+extern "C" size_t nm_neighbor_index_adjacency_workspace_bytes(int64_t n_voxels, int64_t n_records)
+{
+    const int64_t most = (int64_t)1 << 31;
+    if (n_voxels < 0 || n_voxels >= most || n_records < 0 || n_records >= most) return 0;
+    const size_t walk = adj_plan(n_voxels).bytes, rows = adj_rows(n_records).bytes;
+    return walk > rows ? walk : rows;
+}
+
+extern "C" int nm_neighbor_index_adjacency(nm_ctx* ctx, const nm_lattice* lat, double radius, const void* d_work,
+                                           size_t work_bytes, const int64_t* d_label, const double* d_value,
+                                           const int64_t* d_class, int64_t capacity, int64_t* d_key,
+                                           int64_t* d_links, double* d_saddle, int64_t* d_count, void* d_tmp,
+                                           size_t tmp_bytes, void* stream)
+{
+    NM_ENTER_STREAM(ctx, stream);
+    if (!d_label || !d_count) NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_adjacency: bad arguments");
+    const bool emit = d_key != nullptr;
+    if (emit && (!d_links || capacity < 0 || (d_value != nullptr) != (d_saddle != nullptr)))
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_adjacency: the records need d_key, d_links, a capacity >= 0 "
+                "and d_saddle exactly where d_value is given");
+    if (!emit && (d_links || d_saddle))
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_adjacency: d_links or d_saddle without d_key");
+    if (!(radius >= 0.0))      // (NaN fails)
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_adjacency: radius must be >= 0");
+    LatticeDev L;
+    NbrPlan P;
+    int rc = nbr_check_index(ctx, "nm_neighbor_index_adjacency", lat, d_work, work_bytes, &L, &P);
+    if (rc) return rc;
+    int32_t dmin = 0;
+    const int W = nbr_candidate_width(radius, lat->edge, &dmin);
+    if (W < 0) NM_FAIL(ctx, NM_ERR_RADIUS, "radius/edge ratio outside the supported range");
+    if (!d_tmp || tmp_bytes < adj_plan(0).bytes)
+        NM_FAIL(ctx, NM_ERR_WORKSPACE, "nm_neighbor_index_adjacency: temporary workspace too small");
+    const AdjPlan A = adj_plan_of(tmp_bytes);
+    // the scan counts in 32 bits: no voxel has more records than the forward half of its window has cells
+    if ((double)A.room * (0.5 * (double)W * (double)W * (double)W) >= 4294967296.0)
+        NM_FAIL(ctx, NM_ERR_RADIUS, "nm_neighbor_index_adjacency: %lld voxels with %d^3 candidates each could cross "
+                "2^32 edges", (long long)A.room, W);
+    hipStream_t s = (hipStream_t)stream;
+    const char* w = (const char*)d_work;
+    const uint32_t* index_header = (const uint32_t*)w;
+    const uint32_t* leaf = (const uint32_t*)(w + P.off_leaf);
+    const uint32_t* rank = (const uint32_t*)(w + P.off_rank);
+    char* t = (char*)d_tmp;
+    uint32_t* header = (uint32_t*)t;
+    uint32_t* partial = (uint32_t*)(t + A.off_partial);
+    int64_t* addr = (int64_t*)(t + A.off_addr);
+    uint32_t* count = (uint32_t*)(t + A.off_count);
+    const uint32_t room = (uint32_t)A.room;
+    const unsigned blocks = (unsigned)(A.room / 256);
+    const double r2 = radius * radius;
+    if (emit) {
+        // addr[], the scanned count[] and header[0] are the count call's
+        k_adj_walk<true><<<blocks, 256, 0, s>>>(addr, index_header, room, leaf, rank, L, r2, dmin, W, d_label, d_class,
+                                                d_value, count, header, capacity, d_key, d_links, d_saddle, d_count);
+        NM_HIP(ctx, hipGetLastError());
+        return NM_OK;
+    }
+    const uint64_t words = P.superblocks * NM_LEAF_WORDS;
+    NM_HIP(ctx, hipMemsetAsync(d_count, 0, 2 * sizeof(int64_t), s));
+    k_nbr_addresses<<<(unsigned)((words + 255) / 256), 256, 0, s>>>(leaf, rank, index_header, L, words, addr, room);
+    k_adj_walk<false><<<blocks, 256, 0, s>>>(addr, index_header, room, leaf, rank, L, r2, dmin, W, d_label, d_class,
+                                             d_value, count, header, 0, nullptr, nullptr, nullptr, d_count);
+    k_nbr_scan_reduce<<<A.scan_blocks, NBR_SCAN_THREADS, 0, s>>>(count, A.tiles_per_block, A.room, partial);
+    k_nbr_scan_apply<<<A.scan_blocks, NBR_SCAN_THREADS, 0, s>>>(count, A.tiles_per_block, A.room, partial, header,
+                                                                d_count);
+    NM_HIP(ctx, hipGetLastError());
+    return NM_OK;
+}
+
+extern "C" int nm_neighbor_index_adjacency_reduce(nm_ctx* ctx, int64_t n_records, const int64_t* d_key,
+                                                  const int64_t* d_order, const int64_t* d_links_in,
+                                                  const double* d_saddle_in, int64_t* d_pair, int64_t* d_links,
+                                                  double* d_saddle, int64_t* d_count, void* d_tmp, size_t tmp_bytes,
+                                                  void* stream)
+{
+    NM_ENTER_STREAM(ctx, stream);
+    if (n_records < 0 || n_records >= (int64_t)1 << 31 || !d_count ||
+        (n_records > 0 && (!d_key || !d_links_in || !d_pair || !d_links)) ||
+        (d_saddle_in != nullptr) != (d_saddle != nullptr))
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_adjacency_reduce: bad arguments");
+    const AdjRows R = adj_rows(n_records);
+    if (!d_tmp || tmp_bytes < R.bytes)
+        NM_FAIL(ctx, NM_ERR_WORKSPACE, "nm_neighbor_index_adjacency_reduce: temporary workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    NM_HIP(ctx, hipMemsetAsync(d_count, 0, 2 * sizeof(int64_t), s));
+    if (n_records == 0) return NM_OK;
+    char* t = (char*)d_tmp;
+    uint32_t* header = (uint32_t*)t;
+    uint32_t* partial = (uint32_t*)(t + R.off_partial);
+    uint32_t* row = (uint32_t*)(t + R.off_row);
+    unsigned long long* image = (unsigned long long*)d_saddle;
+    const unsigned blocks = (unsigned)(R.rpad / 256);
+    k_adj_heads<<<blocks, 256, 0, s>>>(d_key, n_records, R.rpad, row, d_links, image);
+    k_nbr_scan_reduce<<<R.scan_blocks, NBR_SCAN_THREADS, 0, s>>>(row, R.tiles_per_block, R.rpad, partial);
+    k_nbr_scan_apply<<<R.scan_blocks, NBR_SCAN_THREADS, 0, s>>>(row, R.tiles_per_block, R.rpad, partial, header,
+                                                                d_count);
+    k_adj_reduce<<<blocks, 256, 0, s>>>(d_key, d_order, d_links_in, d_saddle_in, n_records, row, d_pair, d_links,
+                                        image);
+    if (image) k_adj_saddles<<<blocks, 256, 0, s>>>(header, image);
     NM_HIP(ctx, hipGetLastError());
     return NM_OK;
 }

@@ -306,6 +306,12 @@ class NeighborIndex(object):
         .hill_climb(radius, voxel_value, link="highest", ...) -> (labels (M,), sizes (C,), peaks (C,)): every voxel
                                 steps to a higher neighbor, a segment is what climbs to the same peak - it separates
                                 objects that touch, which the three connectivity rules above weld into one
+        .adjacency(radius, labels, voxel_value=None, voxel_class=None) -> (pair (E, 2), links (E,), saddle (E,) or
+                                None): which segments of a labelling touch, over how many voxel edges, and the
+                                highest pass between them - the region adjacency graph, without the lists
+        .prominent_peaks(radius, voxel_value, min_prominence, link="highest", ...) -> (labels (M,), sizes (C,),
+                                peaks (C,), prominence (C,)): hill_climb with the peaks of low prominence merged
+                                into their higher neighbors (topological persistence on adjacency's saddles)
         .component_table(labels, voxel_weight=None) -> (C, 25): one row of descriptors per component (segment_table
                                 over voxels())
     torch in, torch out; numpy in, numpy out (addresses / voxels / point_counts / members / components / dbscan follow the
@@ -854,6 +860,167 @@ class NeighborIndex(object):
             raise ValueError("%s must have one entry per voxel" % what)
         return t.to(device=self._rt.device, dtype=torch.float64).contiguous()
 
+    def _adjacency_device(self, radius, label, value, voxel_class, stages=None):
+        """enqueue nm_neighbor_index_adjacency (count, then records) and nm_neighbor_index_adjacency_reduce around a
+        torch.sort of the records' keys, on device tensors - label int64 (M,), value fp64 (M,) or None, class int64
+        (M,) or None - (pair (E, 2), links (E,), saddle (E,) or None); two host reads: the records, then the rows.
+        stages: a callable(name) the timing tool is told the end of every stage through"""
+        rt = self._rt
+        m = self.n_voxels
+        mark = stages if stages is not None else (lambda name: None)
+        lat = ctypes.byref(self.filter.nm_lattice)
+
+        def empty():
+            return (torch.empty((0, 2), dtype=torch.int64, device=rt.device),
+                    torch.empty(0, dtype=torch.int64, device=rt.device),
+                    None if value is None else torch.empty(0, dtype=torch.float64, device=rt.device))
+
+        if m == 0:
+            return empty()
+        count = torch.empty(2, dtype=torch.int64, device=rt.device)
+        nbytes = int(rt.lib.nm_neighbor_index_adjacency_workspace_bytes(m, 0))
+        tmp = torch.empty(nbytes, dtype=torch.uint8, device=rt.device)
+
+        def walk(capacity, key, links, saddle):
+            rt.check(rt.lib.nm_neighbor_index_adjacency(
+                rt.ctx, lat, radius, _device.ptr(self._work), self._work.numel(), _device.ptr(label),
+                _device.ptr(value), _device.ptr(voxel_class), capacity, _device.ptr(key), _device.ptr(links),
+                _device.ptr(saddle), _device.ptr(count), _device.ptr(tmp), nbytes, rt.stream()))
+
+        walk(0, None, None, None)
+        records, bad = (int(v) for v in count.cpu())
+        if bad < 0:         # (cannot happen: the scratch was sized for this handle's M)
+            raise _ffi.NimrudHipError("nm_neighbor_index_adjacency: scratch too small for the index")
+        if bad:
+            raise ValueError("labels must be below 2^31 (%d are not)" % bad)
+        mark("count")
+        if records == 0:
+            return empty()
+        key = torch.empty(records, dtype=torch.int64, device=rt.device)
+        links = torch.empty(records, dtype=torch.int64, device=rt.device)
+        saddle = None if value is None else torch.empty(records, dtype=torch.float64, device=rt.device)
+        walk(records, key, links, saddle)
+        mark("emit")
+        key, order = torch.sort(key, stable=True)
+        mark("sort")
+        pair = torch.empty((records, 2), dtype=torch.int64, device=rt.device)
+        row_links = torch.empty(records, dtype=torch.int64, device=rt.device)
+        row_saddle = None if value is None else torch.empty(records, dtype=torch.float64, device=rt.device)
+        nbytes_rows = int(rt.lib.nm_neighbor_index_adjacency_workspace_bytes(0, records))
+        tmp_rows = tmp if nbytes_rows <= nbytes else torch.empty(nbytes_rows, dtype=torch.uint8, device=rt.device)
+        rt.check(rt.lib.nm_neighbor_index_adjacency_reduce(
+            rt.ctx, records, _device.ptr(key), _device.ptr(order), _device.ptr(links), _device.ptr(saddle),
+            _device.ptr(pair), _device.ptr(row_links), _device.ptr(row_saddle), _device.ptr(count),
+            _device.ptr(tmp_rows), tmp_rows.numel(), rt.stream()))
+        rows = int(count[0])
+        mark("reduce")
+        # (copies: the rows do not keep the records' memory alive)
+        return (pair[:rows].clone(), row_links[:rows].clone(),
+                None if row_saddle is None else row_saddle[:rows].clone())
+
+    def adjacency(self, radius, labels, voxel_value=None, voxel_class=None):
+        """(pair int64 (E, 2), links int64 (E,), saddle fp64 (E,) or None): the region adjacency graph of a labelling
+        of the voxels - which segments touch, over how many voxel edges, and how high the pass between them lies.
+        the graph is that of components(): voxels u != v are neighbors when lists(voxels(), radius) names one for the
+        other (the limit is inclusive) and both carry the same voxel_class >= 0 (None: one class for all).  labels
+        (integers, (M,)): e.g. what components(), dbscan(), regions() or hill_climb() returned; a negative label is
+        "in no segment"; labels must be below 2^31.  voxel_value (floating point, (M,), as in hill_climb): a voxel
+        with a NaN value is out of the graph; None: no saddle is formed and the third result is None.
+        one row for every unordered pair of distinct labels a < b that at least one edge {u, v} of the graph joins
+        (label[u] = a, label[v] = b): links counts those edges, every undirected edge once; saddle is the largest
+        min(value[u], value[v]) over them - the height of the pass between the two segments.  rows ascend by (a, b);
+        no such pair: arrays of length 0.  no list of the voxel graph is written.  the result is a function of the
+        arguments alone, the same bit for bit on every run."""
+        self._need_index("adjacency")
+        radius = float(radius)
+        if not radius >= 0.0:
+            raise ValueError("radius must be a number >= 0")
+        label = self._voxel_integers(labels, "labels")
+        value = None if voxel_value is None else self._voxel_heights(voxel_value, "voxel_value")
+        cls = None if voxel_class is None else self._voxel_integers(voxel_class, "voxel_class")
+        out = self._adjacency_device(radius, label, value, cls)
+        return out if self._as_torch else tuple(None if t is None else t.cpu().numpy() for t in out)
+
+    def _prominent_peaks_device(self, radius, value, mode, min_prominence, voxel_class, voxel_weight, min_size,
+                                stages=None):
+        """hill_climb, adjacency, the host merge (nm_merge_by_prominence) and the relabelling on device tensors:
+        (labels (M,), sizes (C,), peaks (C,), prominence (C,)).  one copy of the rows and peak values to the host, one
+        copy of the roots and prominences back"""
+        rt = self._rt
+        m = self.n_voxels
+        mark = stages if stages is not None else (lambda name: None)
+        labels0, sizes0, peaks0, _ = self._hill_climb_device(radius, value, mode, voxel_class, None, 1, False)
+        mark("hill_climb")
+        n_seg = int(peaks0.shape[0])
+        if n_seg == 0:      # no voxel in the graph: every label is -1
+            return labels0, sizes0, peaks0, torch.empty(0, dtype=torch.float64, device=rt.device)
+        pair, _, saddle =self._adjacency_device(radius, labels0, value, voxel_class, stages)
+        n_rows = int(pair.shape[0])
+        # down in one piece: pair (2E int64), saddle (E fp64 as their bits), the peaks' values (S fp64 as their bits)
+        packed = torch.cat((pair.reshape(-1), saddle.view(torch.int64), value[peaks0].view(torch.int64))).cpu().numpy()
+        host_pair = np.ascontiguousarray(packed[:2 * n_rows])
+        host_saddle = np.ascontiguousarray(packed[2 * n_rows:3 * n_rows]).view(np.float64)
+        host_peak = np.ascontiguousarray(packed[3 * n_rows:]).view(np.float64)
+        back = np.empty(2 * n_seg, dtype=np.int64)          # root, then the prominences as their bits
+        host_root, host_prom = back[:n_seg], back[n_seg:].view(np.float64)
+        scratch = np.empty(n_rows + n_seg + 1, dtype=np.int64)
+        rc = rt.lib.nm_merge_by_prominence(n_seg, host_peak.ctypes.data, n_rows, host_pair.ctypes.data,
+                                           host_saddle.ctypes.data, min_prominence, scratch.ctypes.data,
+                                           host_root.ctypes.data, host_prom.ctypes.data)
+        if rc:
+            raise _ffi.NimrudHipError("nm_merge_by_prominence: status %d" % rc)
+        mark("merge")
+        back = torch.from_numpy(back).to(rt.device)
+        root, prom = back[:n_seg], back[n_seg:].view(torch.float64)
+        # sizes per root: integer sums, the same in any order
+        inside = labels0 >= 0
+        member_root = root[labels0.clamp(min=0)]
+        size = torch.zeros(n_seg, dtype=torch.int64, device=rt.device)
+        weight = torch.ones(m, dtype=torch.int64, device=rt.device) if voxel_weight is None else voxel_weight
+        size.index_add_(0, member_root[inside], weight[inside])
+        keep = (root == torch.arange(n_seg, device=rt.device)) & (size >= min_size)
+        number = torch.cumsum(keep, 0) - 1
+        labels = torch.where(inside & keep[member_root], number[member_root], torch.full_like(labels0, -1))
+        mark("relabel")
+        return labels, size[keep], peaks0[keep], prom[keep]
+
+    def prominent_peaks(self, radius, voxel_value, min_prominence, link="highest", voxel_class=None,
+                        voxel_weight=None, min_size=1):
+        """(labels int64 (M,), sizes int64 (C,), peaks int64 (C,), prominence fp64 (C,)): hill_climb()'s segments with
+        the peaks of low prominence merged into their higher neighbors - topological persistence.  hill_climb() makes
+        a segment of every local maximum, one stray branch above a crown included; here a peak whose prominence, its
+        value minus the saddle towards a higher neighbor, stays below min_prominence is given back to that neighbor.
+        with link="highest" on height: crown delineation that survives noise; with link="nearest" on dbscan()'s
+        density: ToMATo on quick shift.
+          1. hill_climb(radius, voxel_value, link, voxel_class) gives segments 0..S-1 with peak values p; segment a
+             is HIGHER than b when p[a] > p[b], or they are equal and a < b.
+          2. adjacency(radius, labels, voxel_value, voxel_class) gives the highest saddle between touching segments.
+          3. the rows are taken by descending saddle, equal saddles by ascending (a, b), through a union-find: of the
+             two roots the lower, lo, is merged under the higher when p[lo] - saddle < min_prominence (fp64, strict);
+             otherwise nothing is merged and lo's prominence, if none is recorded yet, is p[lo] - saddle.  a root that
+             never loses has prominence +inf.
+          4. the surviving roots are the segments: a segment's size is the sum of voxel_weight (None: voxels) over
+             its members, segments below min_size are dropped (-1), the others numbered 0..C-1 by ascending peak
+             position; peaks[c] is the root's peak, prominence[c] its prominence.
+        min_prominence is a number >= 0, may be inf.  0 merges nothing: labels, sizes and peaks are hill_climb()'s.
+        inf merges every connected piece of the class graph into its highest peak.  min_size acts AFTER the merge: a
+        small peak merged into a large one lives on inside it.  the result is a function of the arguments alone."""
+        self._need_index("prominent_peaks")
+        radius = float(radius)
+        if not radius >= 0.0:
+            raise ValueError("radius must be a number >= 0")
+        min_prominence = _min_prominence(min_prominence)
+        if isinstance(min_size, bool) or not isinstance(min_size, (int, np.integer)):
+            raise ValueError("min_size must be an integer")
+        if link not in _ffi.NM_CLIMB:
+            raise ValueError("link must be 'highest' or 'nearest'")
+        value = self._voxel_heights(voxel_value, "voxel_value")
+        cls = None if voxel_class is None else self._voxel_integers(voxel_class, "voxel_class")
+        weight = None if voxel_weight is None else self._voxel_integers(voxel_weight, "voxel_weight")
+        out = self._prominent_peaks_device(radius, value, _ffi.NM_CLIMB[link], min_prominence, cls, weight,
+                                           int(min_size))
+        return out if self._as_torch else tuple(t.cpu().numpy() for t in out)
+
     def component_table(self, labels, voxel_weight=None):
         """fp64 (C, 25): segment_table over voxels() for the labels components() returned - one row of descriptors
         per component of the voxel graph (columns: SEGMENT_COLUMNS).  voxels with label -1 are in no segment.
@@ -874,6 +1041,17 @@ def _min_cos(max_angle):
     are never further apart, but the float pi/2 lies below the real one and its cosine, 6e-17, would still cut normals
     that are perpendicular exactly"""
     return math.cos(max_angle) if max_angle < math.pi / 2 else 0.0
+
+
+def _min_prominence(min_prominence):
+    """the threshold of prominent_peaks as a float: a number >= 0, inf included"""
+    try:
+        tau = float(min_prominence)
+    except (TypeError, ValueError):
+        raise ValueError("min_prominence must be a number >= 0")
+    if not tau >= 0.0:      # (NaN fails)
+        raise ValueError("min_prominence must be a number >= 0")
+    return tau
 
 
 def _integer_column(values, n, device, what, per):
@@ -1092,6 +1270,56 @@ def peak_segments(cloud, edge_length, radius, point_value=None, link="highest", 
     peak_xyz = index.filter.address_to_coordinate(index._addresses_device())[peaks]
     peak_value = value[peaks]
     out = (point_labels, sizes, peak_xyz, peak_value)
+    return out if isinstance(cloud, torch.Tensor) else tuple(t.cpu().numpy() for t in out)
+
+
+def prominent_segments(cloud, edge_length, radius, min_prominence, point_value=None, link="highest", point_class=None,
+                       min_points=1):
+    """(point_labels int64 (N,), sizes int64 (C,), peak_xyz fp64 (C, 3), peak_value fp64 (C,), prominence fp64 (C,)):
+    peak_segments with the peaks of low prominence merged into their higher neighbors
+    (NeighborIndex.prominent_peaks): crowns that survive a stray branch, density modes that survive a noisy bin.
+    the cloud is voxel-filtered at `edge_length`; a voxel's value is the MAXIMUM of point_value (floating point, (N,);
+    None: the z column) over its points, its class the MINIMUM of point_class; a peak whose value minus the saddle
+    towards a higher neighboring segment is below min_prominence (a number >= 0, may be inf) goes to that neighbor.
+    every point takes the label of its voxel.  sizes and min_points count POINTS (the voxels are weighted by
+    point_counts()) and act after the merge.  segments are numbered 0..C-1 in ascending order of their peak's voxel
+    position; peak_xyz are the centres of the peak voxels, peak_value their values, prominence what
+    prominent_peaks reports (+inf for the highest peak of a connected piece).
+    one NeighborIndex (method "index"), built and asked once.  torch in, torch out; numpy in, numpy out."""
+    index = NeighborIndex(cloud, edge_length, method="index")
+    rt = index._rt
+    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)):
+        raise ValueError("min_points must be an integer")
+    radius = float(radius)
+    if not radius >= 0.0:
+        raise ValueError("radius must be a number >= 0")
+    min_prominence = _min_prominence(min_prominence)
+    if link not in _ffi.NM_CLIMB:
+        raise ValueError("link must be 'highest' or 'nearest'")
+    n = index._search.shape[0]
+    if point_value is None:
+        column = index._search[:, 2]
+    else:
+        column = torch.as_tensor(point_value)
+        if not column.dtype.is_floating_point:
+            raise ValueError("point_value must have a floating-point dtype")
+        if column.ndim != 1 or column.shape[0] != n:
+            raise ValueError("point_value must have one entry per point")
+        column = column.to(device=rt.device, dtype=torch.float64)
+    value = index.voxel_table(column, reduce="max")[:, 0].contiguous()
+    voxel_class = None
+    if point_class is not None:
+        classes = _integer_column(point_class, n, rt.device, "point_class", "point")
+        # min of an integer-valued fp64 column: exact
+        voxel_class = index.voxel_table(classes.to(torch.float64), reduce="min")[:, 0].to(torch.int64)
+    weight = index._grouping()[0]
+    labels, sizes, peaks, prominence = index._prominent_peaks_device(
+        radius, value, _ffi.NM_CLIMB[link], min_prominence, voxel_class, weight, int(min_points))
+    voxel = index._voxel_of_device(index._search)
+    point_labels = torch.where(voxel >= 0, labels[voxel.clamp(min=0)], torch.full_like(voxel, -1))
+    peak_xyz = index.filter.address_to_coordinate(index._addresses_device())[peaks]
+    peak_value = value[peaks]
+    out = (point_labels, sizes, peak_xyz, peak_value, prominence)
     return out if isinstance(cloud, torch.Tensor) else tuple(t.cpu().numpy() for t in out)
 
 
