@@ -570,6 +570,69 @@ int nm_merge_by_prominence(int64_t n_segments, const double* peak_value, int64_t
                            const double* saddle, double min_prominence, int64_t* scratch, int64_t* root,
                            double* prominence);
 
+/* ---- shortest paths from seeds over the voxel graph: geodesic distance (new symbols only: additive within ABI 7) --
+ * how far a voxel is from the nearest seed ALONG the object - through the voxel graph, around gaps and obstacles, where
+ * nm_neighbor_index_nearest measures straight through them - and which seed that is: trees from their stems, distance
+ * along a wall or a cable, the Voronoi cells of a seed set in the graph metric.  the one query on the index that
+ * iterates: a SWEEP is one full-window walk per voxel, and the number of sweeps depends on the data, so there are two
+ * entry points and the host reads one count between them.  no list is written, nothing is sorted.
+ *   graph: as nm_neighbor_index_components - u ~ v iff the lists, asked with the voxel centres as queries, name one
+ *     for the other (((dx*dx + dy*dy) + dz*dz) <= r*r, inclusive) and both carry the same class >= 0 (d_class NULL =
+ *     class 0 for all).  a voxel of negative class is out of the graph: distance +inf, label -1, link -1.
+ *   edge length: w(u, v) = sqrt(d2), d2 the squared distance of the two centres exactly as the lists' test forms it,
+ *     ((dx*dx + dy*dy) + dz*dz), unfused, and the square root the correctly rounded IEEE one.  w is symmetric in
+ *     (u, v) bit for bit, and w > 0: two centres are an edge apart or more, up to the rounding of the centres.
+ *   seeds: d_seed (uint8[M]); a voxel of the graph with d_seed[v] != 0 has distance 0.  a seed outside the graph is
+ *     ignored.
+ *   distance: dist[v] is the least fixpoint of dist[v] = min over neighbors u of fl(dist[u] + w(u, v)), seeds at 0,
+ *     everything else starting from +inf.  a candidate fl(dist[u] + w) that exceeds max_distance is not taken (the
+ *     limit is inclusive; +inf = no limit), so nothing is reached THROUGH a voxel beyond the limit either.  unreached
+ *     voxels keep +inf.  rounded addition is monotone, so relaxing in any order ends at this one fixpoint: the minimum
+ *     over all paths from a seed of the path's edge lengths summed left to right from the seed, each sum rounded -
+ *     what Dijkstra's algorithm in fp64 returns.  the result is a function of the arguments alone, bit for bit.
+ *   lower(u, v) := dist[u] < dist[v] || (dist[u] == dist[v] && u < v), u and v voxel positions: a strict total order
+ *     on the reached voxels.  every comparison is false for NaN.
+ *   link: for a reached voxel v that is no seed, a neighbor u of its class is a candidate iff
+ *     fl(dist[u] + w(u, v)) == dist[v] and lower(u, v).  link[v] is the candidate with the smallest dist[u], among
+ *     equal ones the smallest position.  link[v] = v at a seed, -1 where v is unreached or out of the graph.  lower
+ *     is part of the test and not inferred from the fixpoint: whatever d_dist holds, links strictly descend a strict
+ *     total order and form no cycle.  a reached voxel that is no seed and has no candidate exists only where d_dist is
+ *     short of the fixpoint: it gets link -1 and label -1, as does (the label) every voxel whose links lead to it,
+ *     and it is counted in d_count[2].
+ *   segments: v belongs to the seed its links lead to.  a segment's size is the sum of d_weight (int64[M], NULL = 1
+ *     each) over its members, the seed included; segments below min_size are dropped: their labels become -1, dist
+ *     and link stay.  kept segments are numbered 0..C-1 in ascending seed position; d_source[c] is that position.
+ *   1. nm_neighbor_index_geodesic_relax: first != 0 initialises d_dist (fp64[M]) from d_seed and writes the voxels'
+ *      addresses into d_tmp; the call then enqueues `sweeps` >= 1 relaxation sweeps, in place.  d_count (int64[1]) =
+ *      the voxels lowered in the LAST sweep of the call: 0 means the fixpoint is reached (and was, before that sweep).
+ *      sweeps queued behind one that lowered nothing return at once.  calls with first == 0 continue on the same
+ *      d_dist with the same arguments and the same d_tmp, untouched in between.  at most M sweeps lower anything.
+ *      d_count[0] = -1, and nothing else is written, where d_tmp has no room for the index's M.
+ *   2. nm_neighbor_index_geodesic_finish: the links from d_dist, then segments, sizes and sources.  d_label[M];
+ *      d_size, d_source (room for M entries each; entries from C on are not touched); d_link[M] (may be NULL: not
+ *      wanted), which does not depend on d_weight or min_size; d_count (int64[3]) = {C = segments kept, seeds in the
+ *      graph, voxels without a candidate}, {-1, -1, -1} and nothing else written where d_tmp has no room for the
+ *      index's M.  the call stands on its own: any d_tmp of the size serves.
+ *   d_tmp: nm_neighbor_index_geodesic_workspace_bytes(M) bytes (16-byte aligned), the size of the components scratch;
+ *     the query needs no GPU, is monotone in M and 0 for M < 0 or M >= 2^31.
+ *   cost: a sweep is one full-window walk per voxel, like the link step of nm_neighbor_index_hill_climb; the number of
+ *     sweeps to the fixpoint is about the largest number of edges on a shortest path.  finish is one such walk and
+ *     the flatten, number and label steps of the components call; the flatten follows every voxel's links to its seed.
+ *   errors, all before anything is queued: NM_ERR_INVALID for a null d_seed, d_dist, d_count (relax), d_dist, d_label,
+ *     d_size, d_source, d_count (finish) or lattice, a NaN or negative radius, a NaN or negative max_distance,
+ *     sweeps < 1; NM_ERR_RADIUS as nm_neighbor_index_lists, NM_ERR_WORKSPACE for too small a d_work or a d_tmp below
+ *     the minimum, NM_ERR_LATTICE as every entry point that takes the index.  nothing here waits for the device. */
+size_t nm_neighbor_index_geodesic_workspace_bytes(int64_t n_voxels);
+int nm_neighbor_index_geodesic_relax(nm_ctx* ctx, const nm_lattice* lat, double radius, const void* d_work,
+                                     size_t work_bytes, const uint8_t* d_seed, const int64_t* d_class,
+                                     double max_distance, int32_t first, int32_t sweeps, double* d_dist,
+                                     int64_t* d_count, void* d_tmp, size_t tmp_bytes, void* stream);
+int nm_neighbor_index_geodesic_finish(nm_ctx* ctx, const nm_lattice* lat, double radius, const void* d_work,
+                                      size_t work_bytes, const int64_t* d_class, const int64_t* d_weight,
+                                      int64_t min_size, const double* d_dist, int64_t* d_label, int64_t* d_size,
+                                      int64_t* d_source, int64_t* d_link, int64_t* d_count, void* d_tmp,
+                                      size_t tmp_bytes, void* stream);
+
 /* ---- per-segment descriptors of a labelled cloud (new symbols only: additive within ABI 7) --------------------
  * what a cluster is as an object: how many points, where, its box, its shape and which way it points.  the last
  * stage behind a classifier and nm_neighbor_index_components; the table is a plain fp64 feature matrix.

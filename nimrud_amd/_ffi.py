@@ -150,6 +150,13 @@ SIGNATURES = {
                                             c_ptr, c_size, c_ptr]),
     "nm_merge_by_prominence": (ctypes.c_int,
                                [c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_f64, c_ptr, c_ptr, c_ptr]),
+    "nm_neighbor_index_geodesic_workspace_bytes": (c_size, [c_i64]),
+    "nm_neighbor_index_geodesic_relax": (ctypes.c_int,
+                                         [c_ptr, _LATP, c_f64, c_ptr, c_size, c_ptr, c_ptr, c_f64, c_i32, c_i32, c_ptr,
+                                          c_ptr, c_ptr, c_size, c_ptr]),
+    "nm_neighbor_index_geodesic_finish": (ctypes.c_int,
+                                          [c_ptr, _LATP, c_f64, c_ptr, c_size, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr,
+                                           c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "nm_segment_table_workspace_bytes": (c_size, [c_i64, c_i64]),
     "nm_segment_table": (ctypes.c_int,
                          [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_size, c_ptr]),

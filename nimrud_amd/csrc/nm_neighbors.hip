@@ -10,6 +10,7 @@
 // and the graph itself: the connected components of the voxels under "within r", by a lock-free union-find, and its
 // density-based clusters (DBSCAN): a density walk, the same union-find on the core voxels, a border walk.
 // and the graph of a labelling's segments: which of them touch, over how many edges, at which saddle (adjacency).
+// and path length over the graph: the shortest way from a set of seeds to every voxel, by relaxation sweeps (geodesic).
 //
 // workspace (nm_neighbor_index_workspace_bytes), S = superblocks of the lattice (at most 2^NM_DENSE_LOG2):
 //   header  256 B      [0] M, written by the scan
@@ -1731,6 +1732,179 @@ __global__ __launch_bounds__(256) void k_adj_saddles(const uint32_t* __restrict_
     ((double*)image)[e] = x;
 }
 
+// ---- geodesic: shortest paths from seeds over the same graph ------------------------------------------------------------
+// dist[v] = the least fixpoint of  dist[v] = min over neighbors u of v's class of fl(dist[u] + w(u, v)),  seeds at 0 and
+// the rest from +inf; w = sqrt(d2), d2 as the walk hands it over (bit-symmetric in u and v: the differences are each
+// other's negatives) and the square root correctly rounded.  rounded addition is monotone, so relaxing in ANY order
+// ends at that one fixpoint: the smallest left-to-right rounded path sum.  the one entry point on the handle that
+// iterates: a SWEEP is one full-window walk per voxel, in place; the host enqueues sweeps in batches and reads one
+// count per batch.
+//
+// a sweep's lane reads its neighbors' distances with relaxed agent-scope loads and stores its own word only.  a value
+// another lane lowers meanwhile may be seen old or new: both are upper bounds of the fixpoint that some path attains,
+// and dist[] only ever falls.  a sweep in which no lane lowered read nothing but the values it started from, which is
+// the fixpoint equation holding everywhere: count 0 = done.
+//
+// tmp: the components layout.  addr[] is written by the relax call that initialises and read by the later ones; the
+// header's words 16..21 are three 64-bit sweep counters used in turn: sweep j of a call adds into j % 3 (the LAST one
+// into d_count[0] instead), reads (j - 1) % 3 and zeroes (j + 1) % 3.  once a sweep has lowered nothing, the sweeps
+// queued behind it return at once: a batch that overshoots the fixpoint costs launches, not walks
+constexpr size_t GEO_COUNTER_BYTES = 64;      // where the three counters start in the header
+
+__device__ __forceinline__ double geo_load(double* p)
+{
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// lower: the strict total order the links descend in - by distance, equal distances (-0 == +0) by the smaller position.
+// false for NaN
+__device__ __forceinline__ bool geo_lower(double dist_u, uint32_t u, double dist_v, uint32_t v)
+{
+    return dist_u < dist_v || (dist_u == dist_v && u < v);
+}
+
+// init: 0 at the seeds of the graph, +inf everywhere else.  nothing where the scratch has no room for the index
+__global__ __launch_bounds__(256) void k_geo_init(const uint32_t* __restrict__ index_header, uint32_t room,
+                                                  const uint8_t* __restrict__ seed, const int64_t* __restrict__ cls,
+                                                  double* __restrict__ dist)
+{
+    const uint32_t m = cc_voxels(index_header, room);
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= m) return;
+    dist[v] = (seed[v] != 0 && !(cls && cls[v] < 0)) ? 0.0 : INFINITY;
+}
+
+// sweep: one lane per voxel, the lists' walk from the voxel's own centre as k_hc_parent runs it.  a neighbor can lower
+// the lane's best only if its own distance is below it (w > 0 and rounding is monotone: fl(du + w) >= du), so the
+// class, the square root and the sum are formed for those alone - in a sweep that changes little, for hardly any.
+// a candidate above max_distance is not taken (+inf: no limit; NaN never gets here).  the walk's own hit at d2 = 0
+// fails the first test.  prev: the count of the sweep before (NULL: there is none in this call); mine: where this
+// sweep counts its lowered lanes, once per wave; next: the counter the sweep behind this one will use
+__global__ __launch_bounds__(256) void k_geo_sweep(const int64_t* __restrict__ addr,
+                                                   const uint32_t* __restrict__ index_header, uint32_t room,
+                                                   const uint32_t* __restrict__ leaf,
+                                                   const uint32_t* __restrict__ rank, LatticeDev L, double r2,
+                                                   int32_t dmin, int32_t W, const int64_t* __restrict__ cls,
+                                                   double max_distance, double* dist,
+                                                   const unsigned long long* prev, unsigned long long* mine,
+                                                   unsigned long long* next)
+{
+    const uint32_t m = index_header[0];
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;       // (room <= 2^31)
+    if (v == 0) {
+        *next = 0ull;
+        if (m > room) *mine = ~0ull;       // the scratch was made for fewer voxels than the index holds: -1
+    }
+    if (m > room) return;
+    if (prev && *prev == 0ull) return;     // the fixpoint was reached before this sweep (the same for every lane)
+    bool lowered = false;
+    if (v < m) {
+        const int64_t c = cls ? cls[v] : 0;
+        const double own = dist[v];        // the lane's own word: nobody else writes it
+        if (c >= 0 && own > 0.0) {         // (a seed cannot fall: no candidate is below 0)
+            int32_t ox, oy, oz;
+            db_cell(addr[v], L, &ox, &oy, &oz);
+            double best = own;
+            nbr_walk_d2(nm_centre(ox, L.min_x, L.edge, L.half_edge), nm_centre(oy, L.min_y, L.edge, L.half_edge),
+                        nm_centre(oz, L.min_z, L.edge, L.half_edge), leaf, rank, L, r2, dmin, W,
+                        [&](uint32_t u, double d2) {
+                            const double du = geo_load(dist + u);
+                            if (!(du < best)) return;
+                            if (cls && cls[u] != c) return;
+                            const double through = du + sqrt(d2);
+                            if (through <= max_distance && through < best) best = through;
+                        });
+            if (best < own) {
+                __hip_atomic_store(dist + v, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                lowered = true;
+            }
+        }
+    }
+    const unsigned long long wave = __ballot(lowered);
+    if (wave && (threadIdx.x & 63) == 0) atomicAdd(mine, (unsigned long long)__popcll(wave));
+}
+
+// link: the same walk with the predicate of the contract.  a neighbor u of v's class is a candidate iff
+// fl(dist[u] + w) == dist[v] AND geo_lower(u, v); the link is the candidate of the smallest distance, among equal ones
+// the smallest position (the walk is in ascending position: "strictly smaller replaces").  NO CYCLE CAN FORM, whatever
+// dist[] holds: geo_lower is part of the test and not inferred from the fixpoint, a link goes to a voxel strictly
+// below v in a strict total order, and a chain of links strictly descends in it.  cc_root in k_cc_flatten follows the
+// links with no other exit than a root, so this is the one place where nothing may be loosened.
+// parent[v]: the link; v itself at a seed (dist == 0, in the graph); CC_NONE for unreached voxels (dist not below
+// +inf: NaN too), voxels out of the graph and the pad.  a reached voxel that is no seed and has no candidate - an
+// ORPHAN, which only a dist[] short of the fixpoint has - is counted in d_count[2], gets link -1 and is its OWN root
+// here: chains of links may end in it, and cc_root must find a root there and not CC_NONE, which it would take for a
+// position.  k_geo_orphans takes the orphans' trees out again behind the flatten.
+// keep[] and size[] are zeroed as k_hc_parent zeroes them; d_count is zeroed by the host
+__global__ __launch_bounds__(256) void k_geo_link(const int64_t* __restrict__ addr,
+                                                  const uint32_t* __restrict__ index_header, uint32_t room,
+                                                  const uint32_t* __restrict__ leaf,
+                                                  const uint32_t* __restrict__ rank, LatticeDev L, double r2,
+                                                  int32_t dmin, int32_t W, const int64_t* __restrict__ cls,
+                                                  const double* __restrict__ dist, uint32_t* __restrict__ parent,
+                                                  uint32_t* __restrict__ keep, int64_t* __restrict__ size,
+                                                  int64_t* __restrict__ link, int64_t* __restrict__ d_count)
+{
+    const uint32_t m = cc_voxels(index_header, room);
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;       // (the grid is room / 256 blocks: v < room)
+    keep[v] = 0u;
+    size[v] = 0;
+    uint32_t up = CC_NONE;
+    bool orphan = false;
+    if (v < m) {
+        const int64_t c = cls ? cls[v] : 0;
+        const double own = dist[v];
+        if (c >= 0 && own < INFINITY) {
+            if (own == 0.0) {
+                up = v;
+            } else {
+                int32_t ox, oy, oz;
+                db_cell(addr[v], L, &ox, &oy, &oz);
+                uint32_t best = CC_NONE;
+                double best_dist = 0.0;
+                nbr_walk_d2(nm_centre(ox, L.min_x, L.edge, L.half_edge), nm_centre(oy, L.min_y, L.edge, L.half_edge),
+                            nm_centre(oz, L.min_z, L.edge, L.half_edge), leaf, rank, L, r2, dmin, W,
+                            [&](uint32_t u, double d2) {
+                                const double du = dist[u];
+                                if (!geo_lower(du, u, own, v)) return;       // (NaN too, and v itself)
+                                if (cls && cls[u] != c) return;
+                                if (!(du + sqrt(d2) == own)) return;
+                                if (best == CC_NONE || du < best_dist) {
+                                    best = u;
+                                    best_dist = du;
+                                }
+                            });
+                orphan = best == CC_NONE;
+                up = orphan ? v : best;
+            }
+        }
+        if (link) link[v] = (up != CC_NONE && !orphan) ? (int64_t)up : -1;
+    }
+    parent[v] = up;
+    const unsigned long long wave = __ballot(orphan);
+    if (wave && (threadIdx.x & 63) == 0)
+        atomicAdd((unsigned long long*)(d_count + 2), (unsigned long long)__popcll(wave));
+}
+
+// behind the flatten every parent[v] is a root: a seed (dist == 0) or an orphan.  whatever hangs below an orphan is in
+// no segment: CC_NONE, the orphan itself too, so that mark, scan, label and k_hc_peaks see the seeds' trees only.
+// every lane reads and writes its own word of parent[].  d_count[2] = -1 where the scratch has no room for the index
+// (k_cc_label does the same for the other two)
+__global__ __launch_bounds__(256) void k_geo_orphans(const uint32_t* __restrict__ index_header, uint32_t room,
+                                                     const double* __restrict__ dist, uint32_t* __restrict__ parent,
+                                                     int64_t* __restrict__ d_count)
+{
+    const uint32_t m = index_header[0];
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m > room) {
+        if (v == 0) d_count[2] = -1;
+        return;
+    }
+    if (v >= m) return;
+    const uint32_t r = parent[v];
+    if (r != CC_NONE && !(dist[r] == 0.0)) parent[v] = CC_NONE;
+}
+
 // argument checks shared by the entry points that take a built workspace
 int nbr_check_index(nm_ctx* ctx, const char* who, const nm_lattice* lat, const void* d_work, size_t work_bytes,
                     LatticeDev* L, NbrPlan* P)
@@ -2442,6 +2616,119 @@ extern "C" int nm_neighbor_index_adjacency_reduce(nm_ctx* ctx, int64_t n_records
     k_adj_reduce<<<blocks, 256, 0, s>>>(d_key, d_order, d_links_in, d_saddle_in, n_records, row, d_pair, d_links,
                                         image);
     if (image) k_adj_saddles<<<blocks, 256, 0, s>>>(header, image);
+    NM_HIP(ctx, hipGetLastError());
+    return NM_OK;
+}
+
+// ---- shortest paths from seeds over the voxel graph (additive within ABI 7) ---------------------------------------------
+
+extern "C" size_t nm_neighbor_index_geodesic_workspace_bytes(int64_t n_voxels)
+{
+    if (n_voxels < 0 || n_voxels >= (int64_t)1 << 31) return 0;
+    return cc_plan(n_voxels).bytes;
+}
+
+extern "C" int nm_neighbor_index_geodesic_relax(nm_ctx* ctx, const nm_lattice* lat, double radius, const void* d_work,
+                                                size_t work_bytes, const uint8_t* d_seed, const int64_t* d_class,
+                                                double max_distance, int32_t first, int32_t sweeps, double* d_dist,
+                                                int64_t* d_count, void* d_tmp, size_t tmp_bytes, void* stream)
+{
+    NM_ENTER_STREAM(ctx, stream);
+    if (!d_seed || !d_dist || !d_count) NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_geodesic_relax: bad arguments");
+    if (!(radius >= 0.0))      // (NaN fails)
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_geodesic_relax: radius must be >= 0");
+    if (!(max_distance >= 0.0))
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_geodesic_relax: max_distance must be >= 0 (+inf: no limit)");
+    if (sweeps < 1) NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_geodesic_relax: sweeps = %d, must be >= 1", sweeps);
+    LatticeDev L;
+    NbrPlan P;
+    int rc = nbr_check_index(ctx, "nm_neighbor_index_geodesic_relax", lat, d_work, work_bytes, &L, &P);
+    if (rc) return rc;
+    int32_t dmin = 0;
+    const int W = nbr_candidate_width(radius, lat->edge, &dmin);
+    if (W < 0) NM_FAIL(ctx, NM_ERR_RADIUS, "radius/edge ratio outside the supported range");
+    if (!d_tmp || tmp_bytes < cc_plan(0).bytes)
+        NM_FAIL(ctx, NM_ERR_WORKSPACE, "nm_neighbor_index_geodesic_relax: temporary workspace too small");
+    const CcPlan C = cc_plan_of(tmp_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    const char* w = (const char*)d_work;
+    const uint32_t* index_header = (const uint32_t*)w;
+    const uint32_t* leaf = (const uint32_t*)(w + P.off_leaf);
+    const uint32_t* rank = (const uint32_t*)(w + P.off_rank);
+    char* t = (char*)d_tmp;
+    unsigned long long* counter = (unsigned long long*)(t + GEO_COUNTER_BYTES);
+    int64_t* addr = (int64_t*)(t + C.off_addr);
+    const uint32_t room = (uint32_t)C.room;
+    const unsigned blocks = (unsigned)(C.room / 256);
+    const double r2 = radius * radius;
+    NM_HIP(ctx, hipMemsetAsync(d_count, 0, sizeof(int64_t), s));
+    NM_HIP(ctx, hipMemsetAsync(counter, 0, 3 * sizeof(unsigned long long), s));
+    if (first) {
+        const uint64_t words = P.superblocks * NM_LEAF_WORDS;
+        k_nbr_addresses<<<(unsigned)((words + 255) / 256), 256, 0, s>>>(leaf, rank, index_header, L, words, addr,
+                                                                        room);
+        k_geo_init<<<blocks, 256, 0, s>>>(index_header, room, d_seed, d_class, d_dist);
+    }
+    for (int32_t j = 0; j < sweeps; ++j)
+        k_geo_sweep<<<blocks, 256, 0, s>>>(addr, index_header, room, leaf, rank, L, r2, dmin, W, d_class, max_distance,
+                                           d_dist, j > 0 ? counter + (j - 1) % 3 : nullptr,
+                                           j + 1 < sweeps ? counter + j % 3 : (unsigned long long*)d_count,
+                                           counter + (j + 1) % 3);
+    NM_HIP(ctx, hipGetLastError());
+    return NM_OK;
+}
+
+extern "C" int nm_neighbor_index_geodesic_finish(nm_ctx* ctx, const nm_lattice* lat, double radius, const void* d_work,
+                                                 size_t work_bytes, const int64_t* d_class, const int64_t* d_weight,
+                                                 int64_t min_size, const double* d_dist, int64_t* d_label,
+                                                 int64_t* d_size, int64_t* d_source, int64_t* d_link,
+                                                 int64_t* d_count, void* d_tmp, size_t tmp_bytes, void* stream)
+{
+    NM_ENTER_STREAM(ctx, stream);
+    if (!d_dist || !d_label || !d_size || !d_source || !d_count)
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_geodesic_finish: bad arguments");
+    if (!(radius >= 0.0))      // (NaN fails)
+        NM_FAIL(ctx, NM_ERR_INVALID, "nm_neighbor_index_geodesic_finish: radius must be >= 0");
+    LatticeDev L;
+    NbrPlan P;
+    int rc = nbr_check_index(ctx, "nm_neighbor_index_geodesic_finish", lat, d_work, work_bytes, &L, &P);
+    if (rc) return rc;
+    int32_t dmin = 0;
+    const int W = nbr_candidate_width(radius, lat->edge, &dmin);
+    if (W < 0) NM_FAIL(ctx, NM_ERR_RADIUS, "radius/edge ratio outside the supported range");
+    if (!d_tmp || tmp_bytes < cc_plan(0).bytes)
+        NM_FAIL(ctx, NM_ERR_WORKSPACE, "nm_neighbor_index_geodesic_finish: temporary workspace too small");
+    const CcPlan C = cc_plan_of(tmp_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    const char* w = (const char*)d_work;
+    const uint32_t* index_header = (const uint32_t*)w;
+    const uint32_t* leaf = (const uint32_t*)(w + P.off_leaf);
+    const uint32_t* rank = (const uint32_t*)(w + P.off_rank);
+    char* t = (char*)d_tmp;
+    uint32_t* header = (uint32_t*)t;
+    uint32_t* partial = (uint32_t*)(t + C.off_partial);
+    int64_t* addr = (int64_t*)(t + C.off_addr);
+    int64_t* size = (int64_t*)(t + C.off_size);
+    uint32_t* parent = (uint32_t*)(t + C.off_parent);
+    uint32_t* keep = (uint32_t*)(t + C.off_keep);
+    const uint32_t room = (uint32_t)C.room;
+    const unsigned blocks = (unsigned)(C.room / 256);
+    const uint64_t words = P.superblocks * NM_LEAF_WORDS;
+    NM_HIP(ctx, hipMemsetAsync(d_count, 0, 3 * sizeof(int64_t), s));
+    // (the addresses again: the call stands on its own, whatever scratch the distances were made with)
+    k_nbr_addresses<<<(unsigned)((words + 255) / 256), 256, 0, s>>>(leaf, rank, index_header, L, words, addr, room);
+    // the forest: every voxel's link towards its seed (in the place of k_cc_init and k_cc_link)
+    k_geo_link<<<blocks, 256, 0, s>>>(addr, index_header, room, leaf, rank, L, radius * radius, dmin, W, d_class,
+                                      d_dist, parent, keep, size, d_link, d_count);
+    k_cc_flatten<<<(unsigned)(C.room / CC_FLAT_THREADS), CC_FLAT_THREADS, 0, s>>>(index_header, room, d_weight,
+                                                                                  parent, size);
+    k_geo_orphans<<<blocks, 256, 0, s>>>(index_header, room, d_dist, parent, d_count);
+    k_cc_mark<<<blocks, 256, 0, s>>>(index_header, room, parent, size, min_size, keep, d_count);
+    k_nbr_scan_reduce<<<C.scan_blocks, NBR_SCAN_THREADS, 0, s>>>(keep, C.tiles_per_block, C.room, partial);
+    k_nbr_scan_apply<<<C.scan_blocks, NBR_SCAN_THREADS, 0, s>>>(keep, C.tiles_per_block, C.room, partial, header,
+                                                                d_count);
+    k_cc_label<<<blocks, 256, 0, s>>>(index_header, room, parent, size, min_size, keep, d_label, d_size, d_count);
+    k_hc_peaks<<<blocks, 256, 0, s>>>(index_header, room, parent, size, min_size, keep, d_source);
     NM_HIP(ctx, hipGetLastError());
     return NM_OK;
 }

@@ -312,6 +312,9 @@ class NeighborIndex(object):
         .prominent_peaks(radius, voxel_value, min_prominence, link="highest", ...) -> (labels (M,), sizes (C,),
                                 peaks (C,), prominence (C,)): hill_climb with the peaks of low prominence merged
                                 into their higher neighbors (topological persistence on adjacency's saddles)
+        .geodesic(radius, voxel_seed, max_distance=None, ...) -> (distance (M,), labels (M,), sizes (C,), sources (C,)):
+                                the length of the shortest path from a seed to every voxel through the graph, and the
+                                seed it starts from - segments grown from seeds (trees from their stems)
         .component_table(labels, voxel_weight=None) -> (C, 25): one row of descriptors per component (segment_table
                                 over voxels())
     torch in, torch out; numpy in, numpy out (addresses / voxels / point_counts / members / components / dbscan follow the
@@ -860,6 +863,114 @@ class NeighborIndex(object):
             raise ValueError("%s must have one entry per voxel" % what)
         return t.to(device=self._rt.device, dtype=torch.float64).contiguous()
 
+    def _voxel_seeds(self, values, what):
+        """bool or integers with one entry per voxel as a uint8 device tensor (M,): 1 where non-zero"""
+        if isinstance(values, torch.Tensor) and values.dtype == torch.bool:
+            values = values.to(torch.uint8)
+        elif not isinstance(values, torch.Tensor) and np.asarray(values).dtype == np.bool_:
+            values = np.asarray(values).astype(np.uint8)
+        return (self._voxel_integers(values, what) != 0).to(torch.uint8)
+
+    # sweeps per nm_neighbor_index_geodesic_relax call: the first batch, the factor the next ones grow by, the largest.
+    # sweeps queued behind the fixpoint return at once, so a generous batch costs launches only
+    _GEODESIC_BATCHES = (8, 2, 256)
+
+    def _geodesic_device(self, radius, seed, max_distance, voxel_class, voxel_weight, min_size, want_link,
+                         stages=None):
+        """enqueue nm_neighbor_index_geodesic_relax in batches until a batch's last sweep lowers nothing, then
+        nm_neighbor_index_geodesic_finish, on device tensors - seed uint8 (M,), class and weight int64 (M,) or None -
+        (distance, labels, sizes, sources, link or None); one host read per batch and one of finish's counts.
+        stages: a callable(name, sweeps) the timing tool is told the end of every stage through"""
+        rt = self._rt
+        m = self.n_voxels
+        mark = stages if stages is not None else (lambda name, sweeps: None)
+        dist = torch.empty(m, dtype=torch.float64, device=rt.device)
+        labels = torch.empty(m, dtype=torch.int64, device=rt.device)
+        sizes = torch.empty(max(m, 1), dtype=torch.int64, device=rt.device)
+        sources = torch.empty(max(m, 1), dtype=torch.int64, device=rt.device)
+        link = torch.empty(m, dtype=torch.int64, device=rt.device) if want_link else None
+        if m == 0:
+            return dist, labels, sizes[:0], sources[:0], link
+        lat = ctypes.byref(self.filter.nm_lattice)
+        count = torch.empty(3, dtype=torch.int64, device=rt.device)
+        nbytes = int(rt.lib.nm_neighbor_index_geodesic_workspace_bytes(m))
+        # (its own: the addresses in it must outlive the host reads between the batches)
+        tmp = torch.empty(nbytes, dtype=torch.uint8, device=rt.device)
+        batch, grow, most = self._GEODESIC_BATCHES
+        done, first = 0, 1
+        while True:
+            if done > m + 1:        # (Bellman-Ford: at most M - 1 sweeps lower anything)
+                raise _ffi.NimrudHipError("nm_neighbor_index_geodesic_relax: no fixpoint after %d sweeps of %d voxels"
+                                          % (done, m))
+            sweeps = min(batch, m + 2 - done)
+            rt.check(rt.lib.nm_neighbor_index_geodesic_relax(
+                rt.ctx, lat, radius, _device.ptr(self._work), self._work.numel(), _device.ptr(seed),
+                _device.ptr(voxel_class), max_distance, first, sweeps, _device.ptr(dist), _device.ptr(count),
+                _device.ptr(tmp), nbytes, rt.stream()))
+            done += sweeps
+            first = 0
+            lowered = int(count[0])
+            mark("relax", sweeps)
+            if lowered < 0:     # (cannot happen: the scratch was sized for this handle's M)
+                raise _ffi.NimrudHipError("nm_neighbor_index_geodesic_relax: scratch too small for the index")
+            if lowered == 0:
+                break
+            batch = min(batch * grow, most)
+        rt.check(rt.lib.nm_neighbor_index_geodesic_finish(
+            rt.ctx, lat, radius, _device.ptr(self._work), self._work.numel(), _device.ptr(voxel_class),
+            _device.ptr(voxel_weight), min_size, _device.ptr(dist), _device.ptr(labels), _device.ptr(sizes),
+            _device.ptr(sources), _device.ptr(link), _device.ptr(count), _device.ptr(tmp), nbytes, rt.stream()))
+        kept, _, orphans = (int(v) for v in count.cpu())
+        mark("finish", 0)
+        if kept < 0:
+            raise _ffi.NimrudHipError("nm_neighbor_index_geodesic_finish: scratch too small for the index")
+        if orphans:
+            raise _ffi.NimrudHipError("nm_neighbor_index_geodesic_finish: %d reached voxels without a link: the "
+                                      "distances are not at their fixpoint" % orphans)
+        return dist, labels, sizes[:kept], sources[:kept], link
+
+    def geodesic(self, radius, voxel_seed, max_distance=None, voxel_class=None, voxel_weight=None, min_size=1,
+                 return_link=False):
+        """(distance fp64 (M,), labels int64 (M,), sizes int64 (C,), sources int64 (C,)) and, with return_link, link
+        int64 (M,): shortest paths from seeds over the voxel graph of components() - voxels u and v are neighbors when
+        lists(voxels(), radius) names one for the other and both carry the same voxel_class >= 0 (None: one class for
+        all); a voxel of negative class is out of the graph: distance +inf, label -1, link -1.  an edge is as long as
+        its two centres are apart: sqrt((dx*dx + dy*dy) + dz*dz), the squared distance as lists() forms it.
+        voxel_seed (bool or integers, (M,)): non-zero makes a voxel of the graph a seed, at distance 0.  distance[v] is
+        the length of the shortest path from any seed to v THROUGH the graph - around gaps and obstacles, where
+        nearest() measures through them: the least fixpoint of distance[v] = min over neighbors u of
+        fl(distance[u] + w(u, v)), which is what Dijkstra's algorithm in fp64 returns (scipy.sparse.csgraph.dijkstra
+        with min_only), bit for bit.  max_distance (a number >= 0; None or inf: no limit): a path longer than that is
+        not taken - the limit is inclusive - and nothing is reached through a voxel beyond it.  unreached voxels keep
+        +inf, label -1 and link -1.
+        u is LOWER than v when distance[u] < distance[v], or they are equal and u < v.  link[v] is, among the neighbors
+        u of v's class that are lower than v and have fl(distance[u] + w(u, v)) == distance[v], the one of the
+        smallest distance, then of the smallest position; v itself at a seed.  a segment is everything whose links lead
+        to the same seed: the Voronoi cells of the seeds in the graph metric - trees from their stems where the crowns
+        interlock, with the stem voxels as seeds.  a voxel equally far from two seeds goes by that rule, never by the
+        order anything ran in.  a segment's size is the sum of voxel_weight (integers, (M,); None counts voxels) over
+        its members; segments below min_size are dropped: their members get -1, distance and link stay.  kept
+        segments are numbered 0..C-1 in ascending order of their seed's position, sources[c] is that position.
+        the work is relaxation sweeps, one full-window walk per voxel each, about as many as the longest shortest
+        path has edges; they are enqueued in growing batches, and the call SYNCHRONISES ONCE PER BATCH to read how many
+        voxels the batch's last sweep lowered (and once more for the counts of the segments).  the result is a
+        function of the arguments alone, the same bit for bit on every run."""
+        self._need_index("geodesic")
+        radius = float(radius)
+        if not radius >= 0.0:
+            raise ValueError("radius must be a number >= 0")
+        if isinstance(min_size, bool) or not isinstance(min_size, (int, np.integer)):
+            raise ValueError("min_size must be an integer")
+        max_distance = float("inf") if max_distance is None else float(max_distance)
+        if not max_distance >= 0.0:
+            raise ValueError("max_distance must be a number >= 0, or None")
+        seed = self._voxel_seeds(voxel_seed, "voxel_seed")
+        cls = None if voxel_class is None else self._voxel_integers(voxel_class, "voxel_class")
+        weight = None if voxel_weight is None else self._voxel_integers(voxel_weight, "voxel_weight")
+        out = self._geodesic_device(radius, seed, max_distance, cls, weight, int(min_size), bool(return_link))
+        out = out if return_link else out[:4]
+        return out if self._as_torch else tuple(t.cpu().numpy() for t in out)
+
     def _adjacency_device(self, radius, label, value, voxel_class, stages=None):
         """enqueue nm_neighbor_index_adjacency (count, then records) and nm_neighbor_index_adjacency_reduce around a
         torch.sort of the records' keys, on device tensors - label int64 (M,), value fp64 (M,) or None, class int64
@@ -1320,6 +1431,55 @@ def prominent_segments(cloud, edge_length, radius, min_prominence, point_value=N
     peak_xyz = index.filter.address_to_coordinate(index._addresses_device())[peaks]
     peak_value = value[peaks]
     out = (point_labels, sizes, peak_xyz, peak_value, prominence)
+    return out if isinstance(cloud, torch.Tensor) else tuple(t.cpu().numpy() for t in out)
+
+
+def geodesic_segments(cloud, edge_length, radius, point_seed, max_distance=None, point_class=None, min_points=1):
+    """(point_distance fp64 (N,), point_labels int64 (N,), sizes int64 (C,), source_xyz fp64 (C, 3)): segments grown
+    from seed points along the object, in one call - individual trees from their stems where the crowns interlock,
+    the distance along a wall or a cable from a marked start.  the cloud is voxel-filtered at `edge_length`; a voxel
+    is a seed if ANY of its points has a non-zero point_seed (bool or integers, (N,)); NeighborIndex.geodesic gives
+    every voxel the length of its shortest path from a seed through the voxels within `radius` of each other (not
+    beyond max_distance, see there) and the seed that path starts from.  every point takes the distance and the label
+    of its voxel: +inf and -1 where no path reaches.  sizes and min_points count POINTS (the voxels are weighted by
+    point_counts()): segments of fewer points are dropped, their points get -1 and keep their distance.  segments are
+    numbered 0..C-1 in ascending order of their seed's voxel position; source_xyz are the centres of the seed voxels.
+    point_class as in cluster_cloud: a voxel's class is the MINIMUM class of the points in it, paths stay within a
+    class, a negative class is out.
+    one NeighborIndex (method "index"), built once; the call synchronises once per batch of sweeps, as geodesic does.
+    torch in, torch out; numpy in, numpy out."""
+    index = NeighborIndex(cloud, edge_length, method="index")
+    rt = index._rt
+    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)):
+        raise ValueError("min_points must be an integer")
+    radius = float(radius)
+    if not radius >= 0.0:
+        raise ValueError("radius must be a number >= 0")
+    max_distance = float("inf") if max_distance is None else float(max_distance)
+    if not max_distance >= 0.0:
+        raise ValueError("max_distance must be a number >= 0, or None")
+    n = index._search.shape[0]
+    if isinstance(point_seed, torch.Tensor) and point_seed.dtype == torch.bool:
+        point_seed = point_seed.to(torch.uint8)
+    elif not isinstance(point_seed, torch.Tensor) and np.asarray(point_seed).dtype == np.bool_:
+        point_seed = np.asarray(point_seed).astype(np.uint8)
+    marks = (_integer_column(point_seed, n, rt.device, "point_seed", "point") != 0).to(torch.float64)
+    # max of a 0 / 1 fp64 column: exact
+    seed = (index.voxel_table(marks, reduce="max")[:, 0] != 0.0).to(torch.uint8)
+    voxel_class = None
+    if point_class is not None:
+        classes = _integer_column(point_class, n, rt.device, "point_class", "point")
+        # min of an integer-valued fp64 column: exact
+        voxel_class = index.voxel_table(classes.to(torch.float64), reduce="min")[:, 0].to(torch.int64)
+    weight = index._grouping()[0]
+    dist, labels, sizes, sources, _ = index._geodesic_device(radius, seed, max_distance, voxel_class, weight,
+                                                             int(min_points), False)
+    voxel = index._voxel_of_device(index._search)
+    at = voxel.clamp(min=0)
+    point_labels = torch.where(voxel >= 0, labels[at], torch.full_like(voxel, -1))
+    point_distance = torch.where(voxel >= 0, dist[at], torch.full_like(dist[at], float("inf")))
+    source_xyz = index.filter.address_to_coordinate(index._addresses_device())[sources]
+    out = (point_distance, point_labels, sizes, source_xyz)
     return out if isinstance(cloud, torch.Tensor) else tuple(t.cpu().numpy() for t in out)
 
 
